@@ -13,6 +13,13 @@ state of that workload whatever --warmup / --steps are; the W warm-up steps and 
 --scaling weak (default): 4096 envs per GPU.  --scaling strong: 4096 envs in total (BASELINE.json's metric), split over
 the ranks.  Envs are independent: no data-path collective; RCCL is used once at the end to gather per-env returns (through
 the library's own smj_allgather_returns) and for the barrier / max-over-ranks timing.
+
+A plain run does only what the headline figure needs: set-up, settle + pre-roll, W warm-up steps, ONE bracket of exactly K timed
+steps, the result line (with the roofline of those timed launches, from their own HIP events).  --full adds everything else: the
+median of three brackets when K is below one action interval, the other scaling mode at N > 1, the other solver, the MuJoCo parity
+status, the other BASELINE.json configs and the CPU baseline (--no-second-solver / --no-extra / --no-cpu-baseline drop single legs).
+--dump-outputs DIR writes the state the timed steps left (the arrays a caller of sim.step receives, plus the synthetic returns) as
+DIR/<name>.npy, before anything else touches the simulator.
 """
 import argparse
 import json
@@ -403,7 +410,7 @@ def measure_one(args, rank, world, hooks, scaling, gather=None):
     # remainder of the action interval runs between two brackets, so the repetitions differ by their random actions only) and the MEDIAN
     # repetition is reported -- its wall time AND its kernel time (one statistic for ms_per_step and kernel_ms_per_step); every
     # repetition is listed in `timed_region_ms`.
-    reps = 3 if args.steps < hold else 1
+    reps = 3 if args.full and args.steps < hold else 1   # a plain run: one bracket, exactly K timed steps
     samples, rep_events = [], []
     for rep in range(reps):
         if rep:
@@ -438,10 +445,10 @@ def measure_one(args, rank, world, hooks, scaling, gather=None):
 
 def measure_ranks(args, rank, world, hooks):
     """The headline measurement (--scaling, default strong: BASELINE.json's 4096 envs IN TOTAL) and, at N > 1, the other scaling mode
-    beside it (key `other_scaling` of the result: weak = --envs per GPU), measured back to back by the same ranks."""
+    beside it under --full (key `other_scaling` of the result: weak = --envs per GPU), measured back to back by the same ranks."""
     m = measure_one(args, rank, world, hooks, args.scaling)
     m["other_scaling"] = None
-    if world > 1:
+    if world > 1 and args.full:
         other = "weak" if args.scaling == "strong" else "strong"
         from stretch_mujoco_amd import parallel
 
@@ -477,6 +484,35 @@ def line_head(args, world, m):
     }
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # the whole dump, .npy headers included: below 64 MB with a margin
+NPY_HEADER_BYTES = 256          # upper bound of one file's .npy header at these ranks
+
+
+def dump_outputs(out_dir, sim, returns):
+    """--dump-outputs: what the timed path left for its caller after the last timed step -- the state slots sim.step fills ([n, envs],
+    float32; the integer slots as float64, exactly) and the synthetic per-env returns.  Over DUMP_LIMIT_BYTES in all, a fixed seeded
+    sample of the envs is written instead (its column indices, ascending, as env_index.npy)."""
+    import torch
+
+    if torch.device(sim.device).type == "cuda":
+        torch.cuda.synchronize(sim.device)
+    arrs = {"qpos": sim.qpos, "qvel": sim.qvel, "qacc_warmstart": sim.qacc_warmstart, "actuator_length": sim.actuator_length,
+            "actuator_velocity": sim.actuator_velocity, "base_pose": sim.base_pose, "xpose": sim.xpose, "info": sim.info, "nstep": sim.nstep,
+            "returns": returns}
+    arrs = {k: v.detach().cpu().numpy() for k, v in arrs.items()}
+    arrs = {k: v.astype(np.float64 if v.dtype.kind in "iu" else np.float32) for k, v in arrs.items()}
+    B = arrs["qpos"].shape[-1]
+    per_env = sum(v.nbytes for v in arrs.values()) / B
+    budget = DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * (len(arrs) + 1)
+    if per_env * B > budget:
+        keep = np.sort(np.random.default_rng(0).choice(B, int(budget // (per_env + 8)), replace=False))
+        arrs = {k: v[..., keep] for k, v in arrs.items()}
+        arrs["env_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,15 +520,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default): --envs in total, split over the ranks -- BASELINE.json's metric is 4096 envs at 1 / 2 / 4 / 8 GPUs; at N > 1 the same "
-                         "line also carries the weak figure (--envs per GPU) under `weak`.  weak: --envs per GPU is `value`")
+                         "line also carries the weak figure (--envs per GPU) under `weak` (with --full).  weak: --envs per GPU is `value`")
     ap.add_argument("--envs", "--envs-per-gpu", dest="envs", type=int, default=4096)
     ap.add_argument("--hold", type=int, default=50, help="physics steps per random action (and per launch)")
     ap.add_argument("--solver", choices=["newton", "pgs"], default="newton",
                     help="newton = the reference model's own solver (stretch.xml names none -> MuJoCo default); "
                          "pgs = the solver named by BASELINE.json north_star")
-    ap.add_argument("--no-second-solver", action="store_true", help="skip the short run of the other solver")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other BASELINE.json configs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: median of three brackets at K < --hold, the other scaling mode at N > 1, the other solver, "
+                         "the MuJoCo parity status, the other BASELINE.json configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state the timed steps left as DIR/<name>.npy (rank 0's envs)")
+    ap.add_argument("--no-second-solver", action="store_true", help="with --full: skip the short run of the other solver")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the short runs of the other BASELINE.json configs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     args = ap.parse_args()
 
@@ -566,6 +606,8 @@ def main():
     sim, B, B_total, hold, dt, samples, reps, value = m["sim"], m["B"], m["B_total"], m["hold"], m["dt"], m["samples"], m["reps"], m["value"]
     events, all_events, kern_ms, kern_steps, flags, flagged = m["events"], m["all_events"], m["kern_ms"], m["kern_steps"], m["flags"], m["flagged"]
     all_returns, gather_path, returns = m["all_returns"], m["gather_path"], m["returns"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, returns)
     if rank == 0:
         # roofline of the dominant kernel: algorithmic bytes of the timed launches / their summed duration (HIP events on the
         # launch stream), i.e. 672 B x envs x steps-per-launch / average launch duration
@@ -600,7 +642,7 @@ def main():
             fl = flops.get("flops_per_env_step")
             out["roofline"]["fp32"] = {"flops_per_env_step": fl, "achieved_tflops": fl * B * kern_steps / (kern_ms / 1e3) / 1e12,
                                        "peak_tflops": 157.3, "source": flops.get("source")}
-        if not args.no_second_solver and world == 1:
+        if args.full and not args.no_second_solver and world == 1:
             other = "pgs" if args.solver == "newton" else "newton"
             sim.set_option("solver", {"pgs": 0, "newton": 2}[other])
             n2 = 300   # six launches whatever --steps is: two made the figure swing by 5 %
@@ -619,13 +661,14 @@ def main():
                                    "flags_union": int(((f2 & 1).max() | (f2 & 2).max() | (f2 & 4).max() | (f2 & 8).max()).item()),
                                    "note": "rank 0 only, same workload, measured after the timed region; envs_flagged counts envs that ran out of "
                                            "constraint rows / contacts since the reset (flags are sticky: the Newton phase before contributes none)"}
-        import __graft_entry__ as _ge
-        out["parity_oracle"] = _ge.mujoco_status()
         oc = cb = None
-        if not args.no_extra and world == 1:
+        if args.full:
+            import __graft_entry__ as _ge
+            out["parity_oracle"] = _ge.mujoco_status()
+        if args.full and not args.no_extra and world == 1:
             sim.stop()
             oc = other_configs(B, dev, hold, args.solver)
-        if not args.no_cpu_baseline and world == 1:   # the contract: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the contract: rank 0 at N=1 only
             cb = cpu_baseline(hold, args.cpu_seconds, args.solver)
         if oc and oc.get("stretch_kitchen_robocasa_physics"):
             # config 4 -- the configuration north_star's target sentence is quoted on -- as a top-level key ahead of the long blocks, so that a

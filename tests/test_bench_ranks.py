@@ -49,7 +49,7 @@ class WallEvent:
         return (other.t - self.t) * 1e3
 
 
-def _worker(rank, world, port, out, scaling, steps):
+def _worker(rank, world, port, out, scaling, steps, full):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     import bench
@@ -79,7 +79,7 @@ def _worker(rank, world, port, out, scaling, steps):
         def gather(sim, returns):
             return parallel.gather_returns(returns), "gloo all_gather_into_tensor (CPU test)"
 
-    args = argparse.Namespace(envs=4096, hold=50, steps=steps, warmup=50, scaling=scaling, solver="newton")
+    args = argparse.Namespace(envs=4096, hold=50, steps=steps, warmup=50, scaling=scaling, solver="newton", full=full)
     m = bench.measure_ranks(args, rank, world, Hooks)
     head = bench.line_head(args, world, m)
     own = sum(a.elapsed_time(b) for a, b, _ in m["events"]) / 1e3
@@ -94,13 +94,13 @@ def _worker(rank, world, port, out, scaling, steps):
     dist.destroy_process_group()
 
 
-def _run(tmp_path, world, scaling, steps):
+def _run(tmp_path, world, scaling, steps, full=True):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    out = str(tmp_path / f"ranks_{world}_{scaling}.json")
-    mp.spawn(_worker, args=(world, port, out, scaling, steps), nprocs=world, join=True)
+    out = str(tmp_path / f"ranks_{world}_{scaling}_{int(full)}.json")
+    mp.spawn(_worker, args=(world, port, out, scaling, steps, full), nprocs=world, join=True)
     with open(out) as f:
         return json.load(f)
 
@@ -143,3 +143,14 @@ def test_weak_as_the_headline_when_asked(tmp_path):
     h = ranks[0]["head"]
     assert h["scaling"] == "weak" and h["config"]["envs_total"] == 8192 and h["config"]["envs_per_gpu"] == 4096 and h["metric"].endswith("per MI355X")
     assert h["strong"]["envs_total"] == 4096 and h["strong"]["envs_per_gpu"] == 2048
+
+
+def test_plain_run_times_exactly_k_steps_in_one_bracket_and_nothing_else(tmp_path):
+    """Without --full: one bracket of exactly K steps even below one action interval, no second scaling measurement."""
+    ranks = _run(tmp_path, 2, "strong", 20, full=False)
+    h = ranks[0]["head"]
+    c = h["config"]
+    assert c["envs_total"] == 4096 and c["ranks_seen"] == 2 and len(c["timed_region_ms"]) == 1
+    assert abs(h["ms_per_step"] * 20 - c["timed_region_ms"][0]) < 2e-3
+    assert "weak" not in h and all(r["nsims"] == 1 for r in ranks)
+    assert all(r["nstep"] == 500 + 200 + 50 + 20 for r in ranks)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 evidence: kernel-trace stats of the bench command, then PMC passes in their own runs (never combined with the
 # sys / hip / hsa trace domains); the same for the ray-casting kernels (tools/gpu_render_prof.py).
+set -eo pipefail   # the first profiling run that fails, faults or times out ends the script (and the round that called it)
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/prof
 export TMPDIR=/tmp

@@ -48,7 +48,12 @@ enum smj_slot {
                              (0 none, 1 translate-by, 2 rotate-by, 3 velocity), rows 1-3 start pose x, y, theta, row 4 increment,
                              rows 5-6 v, omega.  Written by the host when a base command is pushed (push_command, :541,:566-568);
                              smj_step runs BaseController.update() inside the kernel after every physics step */
-  SMJ_SLOT_COUNT = 16
+  SMJ_SLOT_CONTACTS = 16, /* optional, ENV-MAJOR fp32 [ld][SMJ_DIM_CONTACT_CAP][SMJ_CONTACT_WORDS], ld >= num_envs: the contact list and
+                             contact forces of the last step (MjData.contact + mj_contactForce), written by smj_step with
+                             SMJ_READ_CONTACTS.  The one slot that is not batch-major: one wavefront writes one env's records, so
+                             env-major makes them one contiguous block per env -- batch-major [word][ld] would turn each lane's
+                             record into 24 scattered 4-byte stores.  Record layout: SMJ_CON_* below */
+  SMJ_SLOT_COUNT = 17
 };
 
 enum smj_dim {
@@ -57,11 +62,33 @@ enum smj_dim {
   SMJ_DIM_NV_MAX = 11,   /* dof capacity of the kernel variant chosen for this model: 32 (standard) or 64 (big) */
   SMJ_DIM_NSAT_MAX = 12, /* satellite capacity of the variant (0: a build without satellites; the debug dump then ends with 6 floats
                             of qacc per satellite slot) */
-  SMJ_DIM_COUNT = 13
+  SMJ_DIM_CONTACT_CAP = 13, /* contact records per env of SMJ_SLOT_CONTACTS: the largest contact capacity of any build a step of this
+                               context can end in -- the primary build or its escalation target (64 for the satellite builds) */
+  SMJ_DIM_COUNT = 14
 };
 
 /* readout flags for smj_step */
-enum { SMJ_READ_IMU = 1, SMJ_READ_LIDAR = 2, SMJ_READ_POSES = 4 };
+enum { SMJ_READ_IMU = 1, SMJ_READ_LIDAR = 2, SMJ_READ_POSES = 4, SMJ_READ_CONTACTS = 8 };
+
+/* One record of SMJ_SLOT_CONTACTS (4-byte words; the ints are int32 bit patterns in the fp32 array).  Records 0 .. INFO[1]-1 of an env
+ * are the contacts of the call's last step, at the instant pull_status reads (its forward pass, before it integrates: what
+ * MjData.contact / efc_force hold after mj_step); records past INFO[1] are stale.  The order is the kernel's (pair table order; the
+ * satellite builds group contacts differently from MuJoCo), not MuJoCo's.  An env flagged for contact overflow
+ * (INFO[3] bit 1) reports the truncated list it simulated.  A step handed over to a larger build is reported by that build (its
+ * count may exceed SMJ_DIM_NCON_MAX).  The slot is not touched by smj_reset: after a reset it is stale until the next smj_step. */
+enum {
+  SMJ_CON_DIST = 0,     /* signed distance (negative: penetration)                                                       */
+  SMJ_CON_POS = 1,      /* 3 words: contact point, world frame                                                           */
+  SMJ_CON_FRAME = 4,    /* 9 words: 3x3 row major; row 0 the normal from geom1 to geom2, rows 1-2 the kernel's tangents   */
+  SMJ_CON_FORCE = 13,   /* 6 words: force in the contact frame as mj_contactForce gives it (elliptic cones: the contact's rows
+                           of efc_force): normal, tangent 1, tangent 2, torsional, rolling 1, rolling 2; zero past condim and
+                           for a contact without constraint rows                                                         */
+  SMJ_CON_GEOM1 = 19,   /* int32: geom1 (fused model)                                                                    */
+  SMJ_CON_GEOM2 = 20,   /* int32: geom2                                                                                  */
+  SMJ_CON_CONDIM = 21,  /* int32: condim used (after any degradation for lack of rows)                                   */
+  SMJ_CON_EFC_ADR = 22, /* int32: first constraint row, -1 when the contact entered no rows                              */
+  SMJ_CONTACT_WORDS = 24 /* word 23 is 0: a record is 96 bytes                                                           */
+};
 
 /* Replaces MjModel.from_xml_path + MjData(model) (mujoco_server.py:252,258): `blob` is the compiled model
  * produced by stretch_mujoco_amd.mjcf_compiler / model_fuse (SMJB format, model_blob.py). */
@@ -83,7 +110,8 @@ int smj_reset(smj_ctx* ctx, const uint8_t* mask_dev, void* stream);
 /* `nsteps` x mj_step (mujoco_server.py:378) for every env with ctrl held constant, one wavefront per env.
  * On return (stream order) the bound ACT_LENGTH / ACT_VELOCITY / BASE_POSE hold what MjData holds after the last mj_step --
  * the values of its forward pass, one step behind qpos, exactly what pull_status reads (mujoco_server.py:465-515) -- and,
- * if requested in read_flags, GYRO/ACCEL (+ LIDAR) hold the sensor values of the last step.  With BASECTL bound the relative
+ * if requested in read_flags, GYRO/ACCEL (+ LIDAR) hold the sensor values of the last step and CONTACTS its contact list and forces
+ * (-5 when a requested readout's slot is unbound).  With BASECTL bound the relative
  * base moves advance inside the launch (BaseController.update after every step) and CTRL's wheel entries are written back. */
 int smj_step(smj_ctx* ctx, int nsteps, unsigned read_flags, void* stream);
 

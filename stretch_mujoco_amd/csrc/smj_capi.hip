@@ -20,6 +20,10 @@
 #include "smj_meshlet.h"
 #include "smj_render.h"
 #include "smj_comm.h"
+static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
+                  SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
+                  SMJ_CR_DIM == SMJ_CON_CONDIM && SMJ_CR_EFC == SMJ_CON_EFC_ADR,
+              "contact record: the kernel's word offsets (smj_model.h) and the header's (include/smj.h)");
 
 struct smj_ctx {
   int device = 0;
@@ -319,12 +323,15 @@ int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ct
   c->caps = caps[c->variant];
   c->layout = smj_stage_layout(c->caps.nvp, c->caps.nbp + c->caps.nsat, c->caps.nsat);
   c->debug_floats = dbg[c->variant];
+  c->state.con_cap = c->caps.ncon;
   if (c->variant <= 3 || c->variant == 5) {
     // escalation target: the same model loaded for the 160-row tall build (standard, 128-row tall) / the 64-column big build (38 / 50 columns) / the 32-satellite build
     int dummy = 0;
-    rc = smj_load_model(blob, nbytes, c->model_esc, up, c->err, c->variant <= 1 ? &tall : c->variant == 5 ? caps + 6 : caps + 4, 1, &dummy);
+    const SmjCaps* esc_caps = c->variant <= 1 ? &tall : c->variant == 5 ? caps + 6 : caps + 4;
+    rc = smj_load_model(blob, nbytes, c->model_esc, up, c->err, esc_caps, 1, &dummy);
     if (rc) return rc;
     c->has_esc = true;
+    if (esc_caps->ncon > c->state.con_cap) c->state.con_cap = esc_caps->ncon;   // a handed-over step ends in the larger build
     void* d = nullptr;
     c->redo_cap = 16 * (size_t)num_envs;   // a 50-step call is 10 chunks per env; longer calls re-allocate (smj_step)
     HIPCHK(c, hipMalloc(&d, sizeof(int) * c->redo_cap));
@@ -430,6 +437,7 @@ int smj_dims(const smj_ctx* c, int* out) {
   out[SMJ_DIM_NBODY] = c->model.nbody_all; out[SMJ_DIM_NLIDAR] = c->model.nlidar; out[SMJ_DIM_NKEY] = c->model.nkey;
   out[SMJ_DIM_NUM_ENVS] = c->num_envs; out[SMJ_DIM_DEBUG_FLOATS] = c->debug_floats; out[SMJ_DIM_NEFC_MAX] = c->caps.nefc;
   out[SMJ_DIM_NCON_MAX] = c->caps.ncon; out[SMJ_DIM_NV_MAX] = c->caps.nvp; out[SMJ_DIM_NCAM] = c->has_render ? c->render.ncam : 0;
+  out[SMJ_DIM_CONTACT_CAP] = c->state.con_cap;
   return 0;
 }
 
@@ -457,6 +465,7 @@ int smj_bind(smj_ctx* c, int slot, void* p, long ld) {
     case SMJ_SLOT_PROF: s.prof = (float*)p; break;
     case SMJ_SLOT_XPOSE: s.xpose = (float*)p; break;
     case SMJ_SLOT_BASECTL: s.bctl = (float*)p; break;
+    case SMJ_SLOT_CONTACTS: break;   // env-major, its own leading dimension; handed to the kernel only by a call that reads it (smj_step)
   }
   return 0;
 }
@@ -495,8 +504,10 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   if ((read_flags & SMJ_READ_IMU) && (!c->state.gyro || !c->state.accel)) return fail(c, -5, "IMU readout requested but GYRO/ACCEL not bound");
   if ((read_flags & SMJ_READ_LIDAR) && !c->state.lidar) return fail(c, -5, "lidar readout requested but LIDAR not bound");
   if ((read_flags & SMJ_READ_POSES) && !c->state.xpose) return fail(c, -5, "pose readout requested but XPOSE not bound");
+  if ((read_flags & SMJ_READ_CONTACTS) && !c->slot_ptr[SMJ_SLOT_CONTACTS]) return fail(c, -5, "contact readout requested but CONTACTS not bound");
   HIPCHK(c, hipSetDevice(c->device));
   DevState st = c->state;
+  st.contacts = (read_flags & SMJ_READ_CONTACTS) ? (float*)c->slot_ptr[SMJ_SLOT_CONTACTS] : nullptr;
   long pose_ld = c->slot_ld[SMJ_SLOT_XPOSE];
   if (read_flags & SMJ_READ_LIDAR) {
     // the lidar is ray-cast by its own kernel from the body poses of the last step

@@ -277,8 +277,16 @@ struct DevState {
   // SMJ_PGSPREV_ROWS identity keys (type | equality / dof / limit record, or contact: pair | ordinal in the pair's manifold | row in
   // the contact), then as many forces.  Read by the next step's warm start (option pgs_dual_ws), whichever variant runs it.
   float* pgsprev;
+  // Contact readout (null = off; smj_step sets it only for a call with SMJ_READ_CONTACTS): env-major [B][con_cap][SMJ_CR_WORDS],
+  // written by whichever workgroup runs the env's last step of the call (include/smj.h SMJ_SLOT_CONTACTS).  con_cap: the largest
+  // contact capacity of the context's primary build and its escalation target.
+  float* contacts;
+  int con_cap;
 };
 enum { SMJ_PGSPREV_ROWS = 320, SMJ_PGSPREV_STRIDE = 2 * SMJ_PGSPREV_ROWS + 4 };
+// contact readout: read flag and word offsets of one record (include/smj.h SMJ_READ_CONTACTS, SMJ_CON_*)
+enum { SMJ_READ_CR = 8, SMJ_CR_DIST = 0, SMJ_CR_POS = 1, SMJ_CR_FRAME = 4, SMJ_CR_FORCE = 13, SMJ_CR_GEOM1 = 19, SMJ_CR_GEOM2 = 20,
+       SMJ_CR_DIM = 21, SMJ_CR_EFC = 22, SMJ_CR_WORDS = 24 };
 #ifndef SMJ_PGS_GUARD
 #define SMJ_PGS_GUARD 1e-10f   // [MJ] mj_solPGS: an update whose cost change comes out above this is undone (A/B builds of tools only)
 #endif

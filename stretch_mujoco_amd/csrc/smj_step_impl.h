@@ -4829,18 +4829,49 @@ struct StepKernel {
         for (int k = 0; k < 3; k++) S.debug[(SMJ_DBG_XPOS + 3 * lane + k) * S.ld + env] = lane < M.nbody ? s.xpos[lane][k] : 0.f;
     }
   }
+  // one contact's geometry in the words of the readout record: dist, pos, frame (row 0 the normal from geom1 to geom2, rows 1-2 the
+  // tangents) -- the debug dump keeps the first seven
+  SMJ_DEV void contact_geom(int c, float* v) const {
+    v[SMJ_CR_DIST] = s.cdist[c];
+    for (int k = 0; k < 3; k++) v[SMJ_CR_POS + k] = s.cpos[c][k];
+    for (int k = 0; k < 9; k++) v[SMJ_CR_FRAME + k] = s.cframe[c][k];
+  }
   SMJ_DEV void dump_contacts() {
     if (!S.debug) return;
     LANES {
       if (lane < NCON) {
         const int c = lane;
-        float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float v[SMJ_CR_FORCE] = {};
+        float code = 0.f;
         if (c < ncon) {
-          v[0] = s.cdist[c]; v[1] = s.cpos[c][0]; v[2] = s.cpos[c][1]; v[3] = s.cpos[c][2];
-          v[4] = s.cframe[c][0]; v[5] = s.cframe[c][1]; v[6] = s.cframe[c][2];
-          v[7] = (float)(s.cdim[c] + 16 * s.cgeom1[c] + 16 * 1024 * s.cgeom2[c]);   // condim | geom1 << 4 | geom2 << 14 (exact in fp32)
+          contact_geom(c, v);
+          code = (float)(s.cdim[c] + 16 * s.cgeom1[c] + 16 * 1024 * s.cgeom2[c]);   // condim | geom1 << 4 | geom2 << 14 (exact in fp32)
         }
-        for (int k = 0; k < 8; k++) S.debug[(SMJ_DBG_CON + 8 * c + k) * S.ld + env] = v[k];
+        for (int k = 0; k < 7; k++) S.debug[(SMJ_DBG_CON + 8 * c + k) * S.ld + env] = v[k];
+        S.debug[(SMJ_DBG_CON + 8 * c + 7) * S.ld + env] = code;
+      }
+    }
+  }
+  // Contact readout (SMJ_READ_CONTACTS): MjData.contact + mj_contactForce of the last step's forward pass, after its solve.  Every
+  // solver path leaves the final row forces in s.ef: Newton's last constraint update writes them there (at the accepted point),
+  // the PGS paths write their sweep registers back before J'f, and the satellite islands sweep in place.  Elliptic cones: the force
+  // in the contact frame is rows cefc .. cefc + condim - 1.  One record per contact, lane = contact, the env's block contiguous.
+  SMJ_DEV void dump_contact_records() {
+    if (!S.contacts) return;
+    float* const out = S.contacts + (size_t)env * (size_t)S.con_cap * SMJ_CR_WORDS;
+    LANES {
+      const int c = lane;
+      if (c < ncon) {
+        float v[SMJ_CR_WORDS];
+        contact_geom(c, v);
+        const int r0 = s.cefc[c], dim = s.cdim[c];
+        for (int k = 0; k < 6; k++) v[SMJ_CR_FORCE + k] = (r0 >= 0 && k < dim) ? s.ef[r0 + k] : 0.f;
+        v[SMJ_CR_GEOM1] = __builtin_bit_cast(float, (int)s.cgeom1[c]);
+        v[SMJ_CR_GEOM2] = __builtin_bit_cast(float, (int)s.cgeom2[c]);
+        v[SMJ_CR_DIM] = __builtin_bit_cast(float, dim);
+        v[SMJ_CR_EFC] = __builtin_bit_cast(float, r0);
+        v[SMJ_CR_WORDS - 1] = 0.f;
+        for (int k = 0; k < SMJ_CR_WORDS; k++) out[SMJ_CR_WORDS * c + k] = v[k];
       }
     }
   }
@@ -4954,6 +4985,9 @@ struct StepKernel {
       TICK(SMJ_PROF_INTEGRATE)
       pc[SMJ_PROF_PGS_SWEEPS] += (float)niter;
     }
+    // the last step's contact list and solved forces are still in LDS (integration and the base controller do not touch them); a
+    // parked step returned above and writes nothing
+    if (read_flags & SMJ_READ_CR) dump_contact_records();
     store_state(nsteps);
     if (S.cost) {   // shader time of this env's launch (units of 64 clocks): the key of the next launch's order (DevState::order)
       const int cst = (int)((smj_clock() - tlaunch) >> 6);

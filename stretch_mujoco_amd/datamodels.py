@@ -123,3 +123,75 @@ class StatusStretchCameras:  # status_stretch_camera.py:10-125 (depth only on th
     @staticmethod
     def default():
         return StatusStretchCameras(time=0, fps=0)
+
+
+@dataclass
+class StatusStretchContacts:
+    """New, without a reference counterpart (like `step` / `reset`): the contact list of every env's last physics step and its
+    constraint forces -- what MuJoCo users read from MjData.contact and mj_contactForce after mj_step.  Every field is a device
+    tensor, not synchronised to the host; C is the record capacity (SMJ_DIM_CONTACT_CAP), entries past `count` are masked off
+    by `valid` and zero.  The order is the kernel's, not MuJoCo's."""
+    time: Any
+    count: Any          # [B] int32: contacts of the last step (INFO[1])
+    valid: Any          # [B, C] bool: contact index < count
+    geom: Any           # [B, C, 2] int32: geom1, geom2 (fused model)
+    body: Any           # [B, C, 2] int64: original MJCF body ids of the geoms (names["body"])
+    dist: Any           # [B, C]
+    pos: Any            # [B, C, 3] world
+    frame: Any          # [B, C, 3, 3] row 0 the normal from geom1 to geom2, rows 1-2 tangents
+    force: Any          # [B, C, 6] contact frame: normal, tangent 1, tangent 2, torsional, rolling 1, rolling 2
+    force_world: Any    # [B, C, 3] linear force on geom2's body, world frame (frame' force[:3]); geom1's body gets the opposite
+    condim: Any = None  # [B, C] int32: condim used
+    efc_adr: Any = None  # [B, C] int32: first constraint row, -1 when the contact entered no rows
+
+    @staticmethod
+    def from_records(records, count, geom_body, time=None) -> "StatusStretchContacts":
+        """Decode the env-major records [B, C, 24] of SMJ_SLOT_CONTACTS (lib.CON word offsets; the int words are int32 bit
+        patterns) with the per-env contact counts [B] and the geom -> MJCF body map [ngeom] (int64), on the records' device."""
+        import torch
+
+        from .lib import CON
+
+        B, C, _ = records.shape
+        ints = records.view(torch.int32)
+        valid = torch.arange(C, device=records.device).unsqueeze(0) < count.to(records.device).long().unsqueeze(1)
+        vf = valid.unsqueeze(-1)
+        zf, zi = torch.zeros((), dtype=records.dtype, device=records.device), torch.zeros((), dtype=torch.int32, device=records.device)
+        geom = torch.where(vf, ints[:, :, CON["GEOM1"]:CON["GEOM2"] + 1], zi)
+        nb = geom_body.shape[0]
+        body = geom_body[geom.long().clamp(0, nb - 1)]
+        frame = torch.where(vf, records[:, :, CON["FRAME"]:CON["FRAME"] + 9], zf).reshape(B, C, 3, 3)
+        force = torch.where(vf, records[:, :, CON["FORCE"]:CON["FORCE"] + 6], zf)
+        fw = (frame.transpose(-1, -2) @ force[..., :3].unsqueeze(-1)).squeeze(-1)
+        return StatusStretchContacts(
+            time=time, count=count, valid=valid, geom=geom, body=body,
+            dist=torch.where(valid, records[:, :, CON["DIST"]], zf), pos=torch.where(vf, records[:, :, CON["POS"]:CON["POS"] + 3], zf),
+            frame=frame, force=force, force_world=fw,
+            condim=torch.where(valid, ints[:, :, CON["CONDIM"]], zi), efc_adr=torch.where(valid, ints[:, :, CON["EFC_ADR"]], zi - 1))
+
+    def _sides(self, body_ids, other_ids=None):
+        """[B, C] masks: the contact's geom2 body is in `body_ids` and its geom1 body in `other_ids` (any when None), and the
+        same with geom1 / geom2 exchanged.  Ids already on the records' device are used as they are (no copy, no host sync)."""
+        import torch
+
+        S = torch.as_tensor(body_ids, dtype=self.body.dtype, device=self.body.device).reshape(-1)
+        b1, b2 = self.body[..., 0], self.body[..., 1]
+        in1, in2 = torch.isin(b1, S), torch.isin(b2, S)
+        if other_ids is None:
+            o1 = o2 = torch.ones_like(in1)
+        else:
+            O = torch.as_tensor(other_ids, dtype=self.body.dtype, device=self.body.device).reshape(-1)
+            o1, o2 = torch.isin(b1, O), torch.isin(b2, O)
+        return in2 & o1 & self.valid, in1 & o2 & self.valid
+
+    def net_force(self, body_ids, other_ids=None):
+        """[B, 3] world-frame net contact force on the bodies `body_ids` from `other_ids` (from everything when None): each
+        contact counts + on geom2's body and - on geom1's, so contacts inside the set cancel."""
+        on2, on1 = self._sides(body_ids, other_ids)
+        sgn = on2.to(self.force_world.dtype) - on1.to(self.force_world.dtype)
+        return (sgn.unsqueeze(-1) * self.force_world).sum(1)
+
+    def touching(self, body_ids, other_ids=None):
+        """[B] bool: a contact between the two sets entered the constraint system (efc_adr >= 0)."""
+        on2, on1 = self._sides(body_ids, other_ids)
+        return ((on2 | on1) & (self.efc_adr >= 0)).any(1)

@@ -4,7 +4,7 @@ Reference: stretch_mujoco/stretch_mujoco_simulator.py:34-534 (client) + stretch_
 The server process, proxies, locks and the realtime sleep (mujoco_server.py:381-384) have no place in a batched
 throughput simulator: one Python object owns PyTorch-ROCm tensors (batch-major, [dim, B]) and drives the HIP
 library through the ctypes C-ABI (lib.py, include/smj.h).  New, without a reference counterpart: `step(n)`,
-`reset(env_ids)`.
+`reset(env_ids)`, and with `contacts=True` the contact readout `pull_contact_data()`, `contact_force()`, `in_contact()`.
 
 Ordering contract kept from `_ctrl_callback` (mujoco_server.py:450-463): commands issued between steps are
 folded into ctrl before the next physics step; status is the post-step readout.
@@ -21,7 +21,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchJoints, StatusStretchSensors
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchJoints, StatusStretchSensors
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -43,7 +43,7 @@ class StretchBatchSimulator:
     def __init__(self, num_envs: int = 1, device: str = "cuda:0", scene: str = "stretch_empty",
                  model_blob_bytes: Optional[bytes] = None, sensors_to_use: Sequence[StretchSensors] = (),
                  cameras_to_use: Sequence[StretchCameras] = (), start_translation=None, start_rotation_quat=None,
-                 debug: bool = False, solver: str = "newton"):
+                 debug: bool = False, solver: str = "newton", contacts: bool = False):
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         if model_blob_bytes is None:
@@ -68,6 +68,7 @@ class StretchBatchSimulator:
         self._start_translation = start_translation
         self._start_rotation_quat = start_rotation_quat
         self._debug = debug
+        self._contacts = bool(contacts)   # contact list + forces of the last step (SMJ_SLOT_CONTACTS), read by pull_contact_data()
         if solver not in ("pgs", "newton"):
             raise ValueError("solver must be 'pgs' (north_star) or 'newton' (the reference model's default)")
         self.solver = solver
@@ -142,6 +143,16 @@ class StretchBatchSimulator:
         self.xpose = torch.zeros(dims[D["NBODY"]] * 12, B, **f)
         _lib.check(L, ctx, L.smj_bind(ctx, S["XPOSE"], ctypes.c_void_p(self.xpose.data_ptr()), B), "smj_bind(XPOSE)")
         self._read_flags |= _lib.READ_POSES
+        if self._contacts:
+            # env-major records [B, cap, 24] (include/smj.h SMJ_CON_*), cap = the largest contact capacity a step can end in
+            self.contact_cap = dims[D["CONTACT_CAP"]]
+            self.contact_records = torch.zeros(B, self.contact_cap, _lib.CONTACT_WORDS, **f)
+            _lib.check(L, ctx, L.smj_bind(ctx, S["CONTACTS"], ctypes.c_void_p(self.contact_records.data_ptr()), B), "smj_bind(CONTACTS)")
+            self._read_flags |= _lib.READ_CONTACTS
+            # geom -> original MJCF body (names["body"]): a fused blob keeps the body each geom was declared in
+            gb = self.model["geom_origbody"] if "geom_origbody" in self.model else self.model["geom_bodyid"]
+            self._geom_body = torch.as_tensor(np.asarray(gb, np.int64).reshape(-1), device=self.device)
+            self._id_cache = {}   # body-name sets of contact_force / in_contact -> device id tensors
         if self._cameras:
             if dims[D["NCAM"]] == 0:
                 raise _lib.SmjError("the model blob carries no render tables: depth cameras are unavailable for this scene")
@@ -296,6 +307,40 @@ class StretchBatchSimulator:
             st = cam.initial_camera_settings
             setattr(out, attr, compute_K(st.field_of_view_vertical_in_degrees, st.sensor_resolution[0], st.sensor_resolution[1]))
         return out
+
+    @_require_connection
+    def pull_contact_data(self) -> StatusStretchContacts:
+        """The contacts of every env's last physics step and their forces (MjData.contact + mj_contactForce after mj_step), as
+        device tensors without a host synchronisation.  Stale after reset() until the next step().  Needs contacts=True."""
+        if not self._contacts:
+            raise _lib.SmjError("the contact readout is off: construct StretchBatchSimulator(..., contacts=True)")
+        return StatusStretchContacts.from_records(self.contact_records, self.info[1], self._geom_body,
+                                                  time=self.nstep.to(torch.float64) * self.timestep)
+
+    def _body_ids(self, bodies) -> torch.Tensor:
+        """MJCF body name(s) -> their ids as a device tensor, cached per name set: a per-step query copies nothing to the device (a
+        pageable host -> device copy would synchronise the stream)."""
+        key = (bodies,) if isinstance(bodies, str) else tuple(bodies)
+        ids = self._id_cache.get(key)
+        if ids is None:
+            names = self.names["body"]
+            for b in key:
+                if b not in names:
+                    raise KeyError(b)
+            ids = torch.tensor([names.index(b) for b in key], dtype=torch.int64).to(self.device)
+            self._id_cache[key] = ids
+        return ids
+
+    @_require_connection
+    def contact_force(self, body, other=None) -> torch.Tensor:
+        """[B, 3] net world-frame contact force on the MJCF body (or bodies) `body` from `other` (body name(s); None: from
+        everything), summed over the last step's contacts: + on geom2's body, - on geom1's."""
+        return self.pull_contact_data().net_force(self._body_ids(body), None if other is None else self._body_ids(other))
+
+    @_require_connection
+    def in_contact(self, body, other=None) -> torch.Tensor:
+        """[B] bool: a contact between `body` and `other` (None: anything) entered the constraint system at the last step."""
+        return self.pull_contact_data().touching(self._body_ids(body), None if other is None else self._body_ids(other))
 
     @_require_connection
     def pull_joint_limits(self) -> dict:

@@ -15,6 +15,7 @@
 
 #include "../../include/smj.h"
 #include "smj_kernels.h"
+#include "smj_variants.h"
 #include "smj_model_load.h"
 #include "smj_bvh.h"
 #include "smj_meshlet.h"
@@ -34,8 +35,8 @@ struct smj_ctx {
   std::string err;
   float* qpos0_dev = nullptr;
   float* stage = nullptr;      // env-major staging copy of the state, [num_envs][layout.stride] (DevState::stage)
-  int variant = 0;             // 0: standard step kernel, 1: tall (its 128-row build, three envs per CU), 2 / 3 / 4: big with 38 / 50 / 64 dof columns, 5 / 6: main tree + up to 16 / 32 satellites (smj_model.h, smj_sat.h)
-  // capacity escalation (standard variant): the model once more with the tall variant's records, and the list of parked envs
+  int variant = 0;             // row of smj_variants (smj_variants.h)
+  // capacity escalation: the model once more with the records of the variant's escalation target, and the list of parked envs
   DevModel model_esc{};
   bool has_esc = false;
   int* redo = nullptr;
@@ -58,7 +59,7 @@ struct smj_ctx {
   int pipeline_big = 1;        // pipelined dispatch for the two-envs-per-CU builds of the big variant too (option "pipeline_big")
   int pipeline = 5;            // chunk length of the pipelined dispatch (DevState::pipe_len; 0 = one workgroup per env for the whole launch)
   bool pollers_always = false; // option "pollers" < 0: send the pollers with every launch (tests)
-  bool prof_warned = false;    // the one-time warning of smj_step: profiling slot bound, PGS kernel without counters
+  bool prof_warned = false;    // the one-time warning of smj_step: profiling slot bound, the PGS kernel launched has no counters
   int pollers = 2;             // tall-variant workgroups that finish parked envs beside the standard kernel (0: the sweep does it all)
   int* progress = nullptr;     // [B] progress, [B] done_steps, [SMJ_SCHED_WORDS] sched (DevState)
   size_t redo_cap = 0;         // entries the escalation list holds
@@ -99,6 +100,34 @@ static int fail(smj_ctx* c, int code, const char* fmt, ...) {
     hipError_t e_ = (call);                                                                 \
     if (e_ != hipSuccess) return fail(c, -2, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
+
+// the builds linked into this library, by SmjBuildId (each translation unit describes itself: smj_step_tu.h)
+static const SmjBuildDesc* const smj_builds[SMJ_B_COUNT] = {
+#define X(tag) &smj_build_##tag,
+    SMJ_BUILDS(X)
+#undef X
+};
+
+// The solver options that live in DevModel: (option name of smj_set_option or "" for none, field, type).  smj_set_option sets the named ones
+// on the primary model, smj_step copies ALL of them onto the escalation model -- one list, so the two kernels cannot run with different options.
+// NOT here: row_limit ("primary_rows"): the escalation target keeps its full capacity.
+#define SMJ_SOLVER_OPTIONS(X)                                                                                                             \
+  X("iterations", iterations, int) X("tolerance", tolerance, float) X("warmstart", warmstart, int) X("pgs_fixed_iter", pgs_fixed_iter, int) \
+  X("qcqp_exact", qcqp_exact, int) X("grad_noise", grad_noise, float) X("pgs_island_stop", pgs_island_stop, int)                            \
+  X("max_contacts_per_pair", max_con_pair, int) X("solver", solver, int) X("convex_pairs", convex_pairs, int) X("multiccd", multiccd, int)  \
+  X("sep_cache", sep_cache, int) X("manifold_cache", manifold_cache, int) X("pgs_dual_warmstart", pgs_dual_ws, int)                         \
+  X("", ls_iterations, int) X("", multi_serial, int) X("", ls_tolerance, float)
+
+// device memory owned by the context (freed in smj_destroy), zeroed
+template <class T>
+static int alloc_zeroed(smj_ctx* c, size_t count, T** out) {
+  void* d = nullptr;
+  HIPCHK(c, hipMalloc(&d, sizeof(T) * count));
+  c->allocs.push_back(d);
+  HIPCHK(c, hipMemset(d, 0, sizeof(T) * count));
+  *out = (T*)d;
+  return 0;
+}
 
 struct DeviceUploader {
   smj_ctx* c;
@@ -307,27 +336,19 @@ int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ct
     }
   }
   DeviceUploader up{c};
-  SmjCaps caps[7] = {{NVP, NBP, NENT, NEFC, NCON, 0, 0}, {}, {}, {}, {}, {}, {}};   // standard, tall, big38, big50, big, sat, sat32 (smj_model.h)
-  int dbg[7] = {SMJ_DEBUG_FLOATS, 0, 0, 0, 0, 0, 0};
-  SmjCaps tall{};   // the 160-row build: escalation target of the standard variant and of the 128-row build
-  int dbg_tall = 0;
-  smj_tall_caps(&tall.nvp, &tall.nbp, &tall.nent, &tall.nefc, &tall.ncon, &dbg_tall);
-  smj_mid_caps(&caps[1].nvp, &caps[1].nbp, &caps[1].nent, &caps[1].nefc, &caps[1].ncon, &dbg[1]);
-  smj_big38_caps(&caps[2].nvp, &caps[2].nbp, &caps[2].nent, &caps[2].nefc, &caps[2].ncon, &dbg[2], &caps[2].nvs);
-  smj_big50_caps(&caps[3].nvp, &caps[3].nbp, &caps[3].nent, &caps[3].nefc, &caps[3].ncon, &dbg[3], &caps[3].nvs);
-  smj_big_caps(&caps[4].nvp, &caps[4].nbp, &caps[4].nent, &caps[4].nefc, &caps[4].ncon, &dbg[4], &caps[4].nvs);
-  smj_sat_caps(&caps[5].nvp, &caps[5].nbp, &caps[5].nent, &caps[5].nefc, &caps[5].ncon, &dbg[5], &caps[5].nsat);
-  smj_sat32_caps(&caps[6].nvp, &caps[6].nbp, &caps[6].nent, &caps[6].nefc, &caps[6].ncon, &dbg[6], &caps[6].nsat);
-  int rc = smj_load_model(blob, nbytes, c->model, up, c->err, caps, 7, &c->variant);
+  SmjCaps caps[SMJ_NVARIANTS];   // a variant's capacities are those of its Newton build
+  for (int v = 0; v < SMJ_NVARIANTS; v++) caps[v] = smj_builds[smj_variants[v].newton]->caps;
+  int rc = smj_load_model(blob, nbytes, c->model, up, c->err, caps, SMJ_NVARIANTS, &c->variant);
   if (rc) return rc;
   c->caps = caps[c->variant];
   c->layout = smj_stage_layout(c->caps.nvp, c->caps.nbp + c->caps.nsat, c->caps.nsat);
-  c->debug_floats = dbg[c->variant];
+  const SmjVariant& V = smj_variants[c->variant];
+  c->debug_floats = smj_builds[V.newton]->debug_floats;
   c->state.con_cap = c->caps.ncon;
-  if (c->variant <= 3 || c->variant == 5) {
+  if (V.escalates()) {
     // escalation target: the same model loaded for the 160-row tall build (standard, 128-row tall) / the 64-column big build (38 / 50 columns) / the 32-satellite build
     int dummy = 0;
-    const SmjCaps* esc_caps = c->variant <= 1 ? &tall : c->variant == 5 ? caps + 6 : caps + 4;
+    const SmjCaps* esc_caps = V.esc_variant != SMJ_NO_VARIANT ? caps + V.esc_variant : &smj_builds[V.esc_build]->caps;
     rc = smj_load_model(blob, nbytes, c->model_esc, up, c->err, esc_caps, 1, &dummy);
     if (rc) return rc;
     c->has_esc = true;
@@ -344,53 +365,14 @@ int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ct
   c->qpos0_dev = const_cast<float*>(m.qpos0);
   c->state.B = num_envs;
   c->state.ld = num_envs;
-  {
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(int) * 2 * (size_t)num_envs));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, sizeof(int) * 2 * (size_t)num_envs));
-    c->cost = (int*)d;
-    c->order = c->cost + num_envs;
-  }
-  {
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(int) * (2 * (size_t)num_envs + SMJ_SCHED_WORDS + 1)));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, sizeof(int) * (2 * (size_t)num_envs + SMJ_SCHED_WORDS + 1)));
-    c->progress = (int*)d;   // + the `hot` word behind sched, which the per-launch memset leaves alone
-  }
-  {
-    void* d = nullptr;
-    const size_t bytes = sizeof(float) * (size_t)c->layout.stride * (size_t)num_envs;
-    HIPCHK(c, hipMalloc(&d, bytes));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, bytes));
-    c->stage = (float*)d;
-  }
-  {   // separating directions of convex pairs, kept between steps (DevState::sepcache)
-    void* d = nullptr;
-    const size_t bytes = sizeof(float) * 4 * SMJ_SEP_SLOTS * (size_t)num_envs;
-    HIPCHK(c, hipMalloc(&d, bytes));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, bytes));
-    c->state.sepcache = (float*)d;
-  }
-  {   // contact manifolds of convex pairs, kept between steps (DevState::mcache)
-    void* d = nullptr;
-    const size_t bytes = sizeof(float) * SMJ_MC_SLOTS * SMJ_MC_WORDS * (size_t)num_envs;
-    HIPCHK(c, hipMalloc(&d, bytes));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, bytes));
-    c->state.mcache = (float*)d;
-  }
-  {   // PGS: the previous step's rows and forces (DevState::pgsprev), 2.6 KB per env
-    void* d = nullptr;
-    const size_t bytes = sizeof(float) * SMJ_PGSPREV_STRIDE * (size_t)num_envs;
-    HIPCHK(c, hipMalloc(&d, bytes));
-    c->allocs.push_back(d);
-    HIPCHK(c, hipMemset(d, 0, bytes));
-    c->state.pgsprev = (float*)d;
-  }
+  const size_t B = (size_t)num_envs;
+  if ((rc = alloc_zeroed(c, 2 * B, &c->cost))) return rc;
+  c->order = c->cost + num_envs;
+  if ((rc = alloc_zeroed(c, 2 * B + SMJ_SCHED_WORDS + 1, &c->progress))) return rc;   // + the `hot` word behind sched, which the per-launch memset leaves alone
+  if ((rc = alloc_zeroed(c, (size_t)c->layout.stride * B, &c->stage))) return rc;
+  if ((rc = alloc_zeroed(c, 4 * SMJ_SEP_SLOTS * B, &c->state.sepcache))) return rc;           // separating directions of convex pairs, kept between steps
+  if ((rc = alloc_zeroed(c, (size_t)SMJ_MC_SLOTS * SMJ_MC_WORDS * B, &c->state.mcache))) return rc;   // contact manifolds of convex pairs, kept between steps
+  if ((rc = alloc_zeroed(c, SMJ_PGSPREV_STRIDE * B, &c->state.pgsprev))) return rc;           // PGS: the previous step's rows and forces, 2.6 KB per env
   return setup_render(c, blob, nbytes);
 }
 
@@ -543,11 +525,9 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   st.redo = esc ? c->redo : nullptr;
   st.cost = c->cost;
   if (esc) {   // the escalation target runs with the same options
-    DevModel& mb = c->model_esc;
-    const DevModel& ms = c->model;
-    mb.iterations = ms.iterations; mb.warmstart = ms.warmstart; mb.pgs_fixed_iter = ms.pgs_fixed_iter; mb.qcqp_exact = ms.qcqp_exact; mb.grad_noise = ms.grad_noise; mb.pgs_island_stop = ms.pgs_island_stop; mb.max_con_pair = ms.max_con_pair;
-    mb.solver = ms.solver; mb.ls_iterations = ms.ls_iterations; mb.convex_pairs = ms.convex_pairs; mb.multiccd = ms.multiccd; mb.multi_serial = ms.multi_serial; mb.sep_cache = ms.sep_cache; mb.manifold_cache = ms.manifold_cache; mb.pgs_dual_ws = ms.pgs_dual_ws;
-    mb.ls_tolerance = ms.ls_tolerance; mb.tolerance = ms.tolerance;
+#define X(name, field, type) c->model_esc.field = c->model.field;
+    SMJ_SOLVER_OPTIONS(X)
+#undef X
   }
   smj_launch_stage(in, c->stage, Y.stride, c->num_envs, st.ld, false, (hipStream_t)stream);
   // Option `chunk` (default 0 = off; kept for experiments): the n steps go out as separate dispatches of `chunk` steps on the
@@ -556,10 +536,9 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   const int chunk = (c->chunk > 0 && !st.debug && !st.prof && c->num_envs > 1024) ? c->chunk : nsteps;
   // Pipelined chunks (standard variant, batches that need more than one round of workgroups): see DevState::pipe_len
   hipStream_t sm = (hipStream_t)stream;
-  // measured: standard +19 % at chunks of 5, tall (2 envs per CU) +7 % at 10, big with 64 columns (1 env per CU, 16 rounds of workgroups) nothing
-  // (three envs per CU: chunks of 8 measured 3 % ahead of 10)
-  const int pipe_len = c->variant >= 2 ? 2 * c->pipeline : c->variant == 1 ? (3 * c->pipeline + 1) / 2 : c->pipeline;
-  const bool pipe = c->variant != 4 && c->variant != 6 && (c->variant < 2 || c->pipeline_big) && c->pipeline > 0 && chunk == nsteps && nsteps > pipe_len && !st.debug && !st.prof && c->num_envs > c->pipe_min_envs;
+  const SmjVariant& V = smj_variants[c->variant];
+  const int pipe_len = V.chunk_len(c->pipeline);
+  const bool pipe = (V.pipelines == SMJ_PIPE_ALWAYS || (V.pipelines == SMJ_PIPE_IF_BIG && c->pipeline_big)) && c->pipeline > 0 && chunk == nsteps && nsteps > pipe_len && !st.debug && !st.prof && c->num_envs > c->pipe_min_envs;
   st.progress = st.done_steps = st.sched = st.hot = nullptr;
   if (esc || pipe) {
     st.progress = c->progress;
@@ -569,9 +548,8 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   }
   st.pipe_len = 0;
   st.pollers = 0;
-  // the 32-satellite build exists twice: both solvers on one wavefront per env, and Newton only on two (smj_kernels_sat32n.hip)
-  typedef int (*Launch32)(const DevModel&, const DevState&, int, unsigned, hipStream_t);
-  auto sat32_of = [&](const DevModel& m) -> Launch32 { return (m.solver == 2 && (c->newton_two_waves & 2) && !st.prof) ? smj_launch_step_sat32n : smj_launch_step_sat32; };
+  // which builds this call launches (the escalation model runs with the primary's options: one routing for both)
+  const SmjRoute route = smj_route(c->variant, c->model.solver, st.prof != nullptr, c->newton_two_waves, c->pgs_two_waves, smj_builds);
   int lrc = 0;
   for (int done = 0; done < nsteps && !lrc; done += chunk) {
     const int k = nsteps - done < chunk ? nsteps - done : chunk;
@@ -603,45 +581,25 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
     // sixteen, any poll interval, any stream priority), and escalations are rare events (0-2 envs per 50-step launch of 4096
     // under random actions, each worth milliseconds when left to the sweep): the pollers leave at once unless one of the last
     // SMJ_HOT_LAUNCHES launches had an escalation (DevState::hot, kept on the device -- the host runs many launches ahead)
-    const bool poll = esc && pipe && c->pollers > 0 && (c->variant == 0 || c->variant == 5);   // (the 16-satellite build hands over to the 32-satellite one the same way)
+    const bool poll = esc && pipe && c->pollers > 0 && route.poller;
     if (poll) {
       // pollers first, on their own stream, so that they are resident when the standard kernel fills the device; should they
       // not be (nothing guarantees it), parked envs are given up to the sweep, as without pollers
       DevState sp = st;
       sp.redo_worker = 2;
-      const int np = c->variant == 5 ? 6 * c->pollers : c->pollers;   // a kitchen's random-action workload parks ~10 envs per launch, each chunk of the large build takes milliseconds
+      const int np = V.poller_mult * c->pollers;
       sp.pollers = c->pollers_always ? -np : np;
       sp.order = nullptr;
       HIPCHK(c, hipEventRecord(c->ev_fork, sm));
       HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-      lrc = c->variant == 5 ? sat32_of(c->model_esc)(c->model_esc, sp, k, fl, c->aux) : smj_launch_step_tall(c->model_esc, sp, k, fl, c->aux);
+      lrc = route.poller->launch(c->model_esc, sp, k, fl, c->aux);
       HIPCHK(c, hipEventRecord(c->ev_join, c->aux));
     }
-    // The primary builds exist once per solver (smj_step_impl.h newton()): the base name carries Newton, the twin PGS.  In a tools build
-    // (csrc/Makefile bigprof) the base name is the profiling copy with BOTH solvers: a PGS launch with the profiling slot bound tries it
-    // first and falls back to the twin when the base build refuses the solver (its launcher returns before launching anything).
-    typedef int (*Launch)(const DevModel&, const DevState&, int, unsigned, hipStream_t);
-    bool prof_dropped = false;
-    auto by_solver = [&](Launch base, Launch twin) -> int {
-      if (c->model.solver == 2) return base(c->model, st, k, fl, sm);
-      if (st.prof) {
-        const int r = base(c->model, st, k, fl, sm);
-        if (r != SMJ_LAUNCH_REFUSED_SOLVER) return r;
-        prof_dropped = true;   // a product build: its base kernel carries Newton only, the PGS twin has no cycle counters compiled in
-      }
-      return twin(c->model, st, k, fl, sm);
-    };
-    if (!lrc)
-      lrc = c->variant == 6   ? sat32_of(c->model)(c->model, st, k, fl, sm)
-            : c->variant == 5 ? by_solver((c->model.solver == 2 && (c->newton_two_waves & 1) && (!st.prof || smj_sat2_profiling())) ? smj_launch_step_sat2 : smj_launch_step_sat, c->pgs_two_waves ? smj_launch_step_satp : smj_launch_step_sat1)
-            : c->variant == 4 ? smj_launch_step_big(c->model, st, k, fl, sm)
-            : c->variant == 3 ? by_solver(smj_launch_step_big50, smj_launch_step_big50p)
-            : c->variant == 2 ? by_solver(smj_launch_step_big38, smj_launch_step_big38p)
-            : c->variant == 1 ? by_solver(smj_launch_step_mid, smj_launch_step_midp)
-            : st.prof         ? smj_launch_step_prof(c->model, st, k, fl, sm)
-                              : by_solver(smj_launch_step, smj_launch_step_pgs);
-    if (lrc == SMJ_LAUNCH_REFUSED_SOLVER) return fail(c, -2, "no kernel of this build carries solver %d for variant %d", c->model.solver, c->variant);
-    if (prof_dropped && !c->prof_warned) {   // (once: the caller asked for stage cycles and gets zeros -- say so instead of returning them silently)
+    // The primary builds exist once per solver (smj_step_impl.h newton()); smj_route has picked the one that carries this call's
+    // solver by what the builds say of themselves -- a launcher's refusal (its own guard) is an error here, not a question.
+    if (!lrc) lrc = route.primary->launch(c->model, st, k, fl, sm);
+    if (lrc == SMJ_LAUNCH_REFUSED_SOLVER) return fail(c, -2, "build `%s` does not carry solver %d (variant %s)", route.primary->tag, c->model.solver, V.name);
+    if (route.no_counters && !c->prof_warned) {   // (once: the caller asked for stage cycles and gets zeros -- say so instead of returning them silently)
       c->prof_warned = true;
       fprintf(stderr, "libsmj: the profiling slot is bound but the PGS kernel of this build has no cycle counters (build `make bigprof` and load it through SMJ_LIB_PATH); the counters stay zero\n");
     }
@@ -651,7 +609,7 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
       // offending step) is finished by the tall variant (160 rows / 48 contacts); an empty list returns at once
       st.redo_worker = 1;
       st.pipe_len = 0;
-      lrc = c->variant <= 1 ? smj_launch_step_tall(c->model_esc, st, k, fl, sm) : c->variant == 5 ? sat32_of(c->model_esc)(c->model_esc, st, k, fl, sm) : smj_launch_step_big(c->model_esc, st, k, fl, sm);
+      lrc = route.sweep->launch(c->model_esc, st, k, fl, sm);
     }
   }
   if (lrc) return fail(c, -2, "step kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
@@ -737,21 +695,7 @@ int smj_render_rgb(smj_ctx* c, int cam, int width, int height, float fovy_deg, v
 int smj_set_option(smj_ctx* c, const char* name, double v) {
   if (!c || !name) return -1;
   DevModel& m = c->model;
-  if (!strcmp(name, "iterations")) m.iterations = (int)v;
-  else if (!strcmp(name, "tolerance")) m.tolerance = (float)v;
-  else if (!strcmp(name, "warmstart")) m.warmstart = (int)v;
-  else if (!strcmp(name, "pgs_fixed_iter")) m.pgs_fixed_iter = (int)v;
-  else if (!strcmp(name, "qcqp_exact")) m.qcqp_exact = (int)v;
-  else if (!strcmp(name, "grad_noise")) m.grad_noise = (float)v;
-  else if (!strcmp(name, "pgs_island_stop")) m.pgs_island_stop = (int)v;
-  else if (!strcmp(name, "max_contacts_per_pair")) m.max_con_pair = (int)v;
-  else if (!strcmp(name, "solver")) m.solver = (int)v;
-  else if (!strcmp(name, "convex_pairs")) m.convex_pairs = (int)v;
-  else if (!strcmp(name, "multiccd")) m.multiccd = (int)v;
-  else if (!strcmp(name, "sep_cache")) m.sep_cache = (int)v;
-  else if (!strcmp(name, "manifold_cache")) m.manifold_cache = (int)v;
-  else if (!strcmp(name, "pgs_dual_warmstart")) m.pgs_dual_ws = (int)v;
-  else if (!strcmp(name, "lidar_cull")) c->lidar_cull = (int)v;                  // 1 (default): per env, only the geoms whose bounding sphere reaches the rangefinders' scan plane are staged
+  if (!strcmp(name, "lidar_cull")) c->lidar_cull = (int)v;                  // 1 (default): per env, only the geoms whose bounding sphere reaches the rangefinders' scan plane are staged
   else if (!strcmp(name, "depth_raster")) c->render.raster = (int)v;            // 0: ray cast the meshes through their BVHs (the round-2 path)
   else if (!strcmp(name, "depth_raster_splits")) c->render.raster_splits = (int)(v < 1 ? 1 : v > 256 ? 256 : v);
   else if (!strcmp(name, "primary_rows")) m.row_limit = (int)v;   // the escalation variant keeps its full capacity (model_esc is not touched)
@@ -770,6 +714,9 @@ int smj_set_option(smj_ctx* c, const char* name, double v) {
     const int n = (int)(v < 0 ? -v : v);
     c->pollers = n > 256 ? 256 : n;
   }
+#define X(opt, field, type) else if ((opt)[0] && !strcmp(name, opt)) m.field = (type)v;
+  SMJ_SOLVER_OPTIONS(X)   // the solver options of DevModel, by the list smj_step copies onto the escalation model
+#undef X
   else return fail(c, -1, "unknown option '%s'", name);
   return 0;
 }

@@ -1,11 +1,8 @@
 // gfx950 kernels of the batched Stretch physics path.  One wavefront (64 lanes) per environment, one
 // workgroup per wavefront; the per-environment working set (body tree, mass-matrix factor, constraint
 // Jacobian, A = J M^-1 J' + R) lives in LDS for the whole launch, model constants stream from L2.
-#include "smj_kernels.h"
-// the standard variant of the step kernel, without the per-stage cycle counters: they are runtime-optional but cost the
-// kernel registers it does not have (scratch 144 -> 48 B per lane); smj_kernels_prof.hip compiles the same kernel with them
-#define SMJ_PROFILING 0
-#define SMJ_ONLY_NEWTON 1   // this translation unit's step kernel carries the Newton solver only; smj_kernels_pgs.hip is its PGS twin (smj_step_impl.h newton())
+// The step kernel in this translation unit is build `step` of the table in smj_builds.h (the standard variant, Newton only).
+#define SMJ_BUILD_TAG step
 #include "smj_step_tu.h"
 
 // mj_resetData for masked envs: batch-major, lanes = envs (coalesced)

@@ -1,13 +1,3 @@
-// The big capacity variant of the step kernel (64 dof lanes, 160 constraint rows, 48 contacts; smj_model.h): scenes with several
-// free objects -- the reference's own scene.xml (table + 2 objects, models/scene.xml:21-35) and the kitchens.  This build: 38 dof columns
-// (the robot + two free objects: scene.xml), under 80 KB of LDS per env: two envs per CU.
-#define SMJ_BIG 1
-#define SMJ_NVS 38
-#define SMJ_VARIANT_TAG big38
-#ifndef SMJ_PROFILING
-#define SMJ_PROFILING 0   // the per-stage cycle counters cost registers; tools build a profiling copy with -DSMJ_PROFILING=1
-#endif
-#if !SMJ_PROFILING
-#define SMJ_ONLY_NEWTON 1   // product build: the Newton solver only; PGS launches go to smj_kernels_big38p.hip (smj_step_impl.h newton()); the profiling copy keeps both
-#endif
+// Build `big38` of the step kernel: what it is stands in the table of smj_builds.h.
+#define SMJ_BUILD_TAG big38
 #include "smj_step_tu.h"

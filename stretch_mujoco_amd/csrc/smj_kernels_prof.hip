@@ -1,5 +1,3 @@
-// The standard variant of the step kernel WITH the per-stage shader-cycle counters (DevState::prof, SMJ_SLOT_PROF): what
-// smj_step launches when the profiling slot is bound (tools/gpu_diag.py).  Same code, same arithmetic.
-#define SMJ_PROFILING 1
-#define SMJ_PROF_TU 1
+// Build `prof` of the step kernel: what it is stands in the table of smj_builds.h.
+#define SMJ_BUILD_TAG prof
 #include "smj_step_tu.h"

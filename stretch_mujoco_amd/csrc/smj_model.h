@@ -4,16 +4,11 @@
 #pragma once
 #include <stdint.h>
 
-// Three capacity variants of the step kernel are compiled from the same source (smj_kernels.hip, smj_kernels_tall.hip,
-// smj_kernels_big.hip):
-//   standard -- the robot alone or with ONE free object: 32 dofs, 80 constraint rows, 16 contacts; 40 KB of LDS per env,
-//               four envs per CU;
-//   tall (SMJ_TALL) -- the same 32 dofs with 160 rows and 48 contacts (~80 KB of LDS, two envs per CU): contact-rich scenes
-//               (kitchen fixtures all around the robot), and the escalation target of the standard variant -- an env whose
-//               step needs more rows / contacts than the standard kernel holds is finished by this one (DevState::redo);
-//   big (SMJ_BIG) -- scenes with several free objects (the reference's own scene.xml: table + 2 objects; kitchens):
-//               64 dofs, 160 rows, 48 contacts; ~130 KB of LDS per env, one env per CU.
-// smj_create picks the variant from the model's dimensions (and the model compiler's capacity hint).
+// The capacity variants of the step kernel are compiled from the same source; which builds exist, and the capacity macros each one
+// sets for the #if ladder below, stands in ONE place: the table of smj_builds.h (a translation unit selects a build with
+// SMJ_BUILD_TAG; none = the standard capacities).  smj_create picks the variant from the model's dimensions (and the model
+// compiler's capacity hint); smj_variants.h says which builds serve a variant.
+#include "smj_builds.h"
 // Satellite builds (SMJ_SAT = satellite capacity, csrc/smj_sat.h, model_fuse.find_satellites): the MAIN tree (the robot: 32 dof lanes /
 // columns, as the standard variant) plus up to SMJ_SAT single-body mechanisms -- free objects, doors, drawers -- that meet it
 // only through contacts.  Each satellite is one LANE (32 + s) with its own 6 x 6 mass block; constraint rows that touch the main

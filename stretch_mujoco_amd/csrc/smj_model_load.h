@@ -45,7 +45,6 @@ struct SmjBlob {
 // Host restatement of what the kernel's stage-table loaders (smj_step_impl.h: KinTab, BodyTab, DofTab, EntryTab, ActTab)
 // used to gather per lane from the individual tables, one record per lane.
 // capacities of a kernel variant (smj_model.h): the loader builds its records for the variant that will run
-struct SmjCaps { int nvp, nbp, nent, nefc, ncon, nvs, nsat; };   // nvs: dof columns of the variant's matrices (0: nvp); nsat: satellite capacity (0: a build without satellites)
 static inline std::vector<int> smj_build_lanerec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
                                                  std::map<std::string, std::vector<float>>& F, int nent) {
   const int LR_ACT = smj_lr_act(nent), LR_STRIDE = smj_lr_stride(nent);

@@ -111,7 +111,7 @@ struct Smem {
 #endif
     } c;
 #if NSAT > 0 && defined(SMJ_ONLY_NEWTON)
-    float pa[4];                            // (a Newton-only build keeps no A: the 18 KB of the triangle are what lets smj_kernels_sat.hip / _sat2.hip carry 112 dense rows in half a CU's LDS)
+    float pa[4];                            // (a Newton-only build keeps no A: without the 18 KB of the triangle the 16-satellite family's Newton builds -- 208 rows, 96 of them dense, smj_builds.h -- fit half a CU's LDS)
 #elif NSAT > 0
     float pa[NEFC_P * (NEFC_P + 1) / 2];   // PGS: A of the dense system, packed lower triangle
 #endif
@@ -4940,6 +4940,7 @@ struct StepKernel {
         for (int pass = 0; pass < 2; pass++) {
           collision_convex(pc, prof && pass == 0);
           if (pass || !((flags & ~flags_planes) & SMJ_FLAG_CON_OVERFLOW) || !(SMJ_SPLIT_COLLIDE || (S.mcache && M.manifold_cache))) break;
+          static_assert(SMJ_MC_SLOTS <= 64, "the redo clears the env's kept manifolds in ONE pass of the 64 lanes (SMJ_MC_LOG2 above 5 needs a loop here)");
           if (S.mcache) {
             LANES { if (lane < SMJ_MC_SLOTS) S.mcache[((size_t)env * SMJ_MC_SLOTS + lane) * SMJ_MC_WORDS] = 0.f; }
           }

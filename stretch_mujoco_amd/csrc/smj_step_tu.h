@@ -1,45 +1,14 @@
-// The step kernel and its launcher for ONE build of ONE capacity variant (smj_model.h): included by smj_kernels.hip (standard),
-// smj_kernels_prof.hip (standard with the per-stage cycle counters), smj_kernels_tall.hip (SMJ_TALL, which also gets the
-// escalation worker kernel) and smj_kernels_big.hip (SMJ_BIG).  Device code is compiled per translation unit, so the
-// instantiations of StepKernel / Smem never meet.
+// The step kernel, its launcher and its descriptor for ONE build of the table in smj_builds.h: a translation unit selects the build
+// (#define SMJ_BUILD_TAG <tag>) and includes this file FIRST.  Device code is compiled per translation unit, so the instantiations of
+// StepKernel / Smem never meet.
 #pragma once
+#ifdef SMJ_BUILDS_INCLUDED
+#error "smj_step_tu.h must be the first include of its translation unit: smj_builds.h has to see SMJ_STEP_TU"
+#endif
+#define SMJ_STEP_TU 1
+#include "smj_builds.h"
 #include "smj_kernels.h"
 #include "smj_step_impl.h"
-
-#define SMJ_CAT2(a, b) a##b
-#define SMJ_CAT(a, b) SMJ_CAT2(a, b)
-#if defined(SMJ_SAT)   // the satellite build (smj_sat.h)
-#define SMJ_STEP_KERNEL SMJ_CAT(smj_step_kernel_, SMJ_VARIANT_TAG)
-#define SMJ_LAUNCH_STEP SMJ_CAT(smj_launch_step_, SMJ_VARIANT_TAG)
-#if SMJ_SAT == 32   // the escalation target of the 16-satellite build (smj_step_kernel_sat32_worker; the two-wavefront Newton build: _sat32n_worker)
-#define SMJ_WORKER_KERNEL SMJ_CAT(SMJ_CAT(smj_step_kernel_, SMJ_VARIANT_TAG), _worker)
-#endif
-#elif defined(SMJ_BIG)   // three builds: SMJ_VARIANT_TAG = big38 / big50 / big (column capacity SMJ_NVS, smj_model.h)
-#define SMJ_STEP_KERNEL SMJ_CAT(smj_step_kernel_, SMJ_VARIANT_TAG)
-#define SMJ_LAUNCH_STEP SMJ_CAT(smj_launch_step_, SMJ_VARIANT_TAG)
-#if SMJ_NVS == 64   // the escalation target of the 38- / 50-column builds
-#define SMJ_WORKER_KERNEL smj_step_kernel_big_worker
-#endif
-#elif defined(SMJ_TALL) && defined(SMJ_TALL_ROWS) && defined(SMJ_ONLY_PGS)   // the 128-row build, PGS-only twin (smj_kernels_midp.hip)
-#define SMJ_STEP_KERNEL smj_step_kernel_midp
-#define SMJ_LAUNCH_STEP smj_launch_step_midp
-#elif defined(SMJ_TALL) && defined(SMJ_TALL_ROWS)   // the 128-row build: primary kernel only, its steps escalate to the 160-row build
-#define SMJ_STEP_KERNEL smj_step_kernel_mid
-#define SMJ_LAUNCH_STEP smj_launch_step_mid
-#elif defined(SMJ_TALL)
-#define SMJ_STEP_KERNEL smj_step_kernel_tall
-#define SMJ_LAUNCH_STEP smj_launch_step_tall
-#define SMJ_WORKER_KERNEL smj_step_kernel_tall_worker   // the escalation target of the standard variant
-#elif defined(SMJ_PROF_TU)
-#define SMJ_STEP_KERNEL smj_step_kernel_prof
-#define SMJ_LAUNCH_STEP smj_launch_step_prof
-#elif defined(SMJ_ONLY_PGS)   // the standard variant's PGS-only build (smj_kernels_pgs.hip)
-#define SMJ_STEP_KERNEL smj_step_kernel_pgs
-#define SMJ_LAUNCH_STEP smj_launch_step_pgs
-#else
-#define SMJ_STEP_KERNEL smj_step_kernel
-#define SMJ_LAUNCH_STEP smj_launch_step
-#endif
 
 // agent-scope relaxed atomics on the scheduling words (coherent across the XCDs' L2s); data handed over with them is fenced
 #define SMJ_ALOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -269,9 +238,7 @@ int SMJ_LAUNCH_STEP(const DevModel& m_in, const DevState& s, int nsteps, unsigne
   return 0;
 }
 
-#if defined(SMJ_BIG)
-// capacities and layouts of this build for the host side (smj_capi.hip is compiled for the standard variant)
-void SMJ_CAT(SMJ_CAT(smj_, SMJ_VARIANT_TAG), _caps)(int* nvp, int* nbp, int* nent, int* nefc, int* ncon, int* debug_floats, int* nvs) {
-  *nvp = NVP; *nbp = NBP; *nent = NENT; *nefc = NEFC; *ncon = NCON; *debug_floats = SMJ_DEBUG_FLOATS; *nvs = NVS;
-}
+// what this object is, for the host side (smj_capi.hip is compiled for the standard family and asks)
+#if !defined(__HIP_DEVICE_COMPILE__)   // host data: the device pass must not see a constant that names a host function
+const SmjBuildDesc SMJ_CAT(smj_build_, SMJ_BUILD_TAG) = SMJ_BUILD_DESC_INIT(SMJ_LAUNCH_STEP);
 #endif

@@ -108,16 +108,6 @@ static const SmjBuildDesc* const smj_builds[SMJ_B_COUNT] = {
 #undef X
 };
 
-// The solver options that live in DevModel: (option name of smj_set_option or "" for none, field, type).  smj_set_option sets the named ones
-// on the primary model, smj_step copies ALL of them onto the escalation model -- one list, so the two kernels cannot run with different options.
-// NOT here: row_limit ("primary_rows"): the escalation target keeps its full capacity.
-#define SMJ_SOLVER_OPTIONS(X)                                                                                                             \
-  X("iterations", iterations, int) X("tolerance", tolerance, float) X("warmstart", warmstart, int) X("pgs_fixed_iter", pgs_fixed_iter, int) \
-  X("qcqp_exact", qcqp_exact, int) X("grad_noise", grad_noise, float) X("pgs_island_stop", pgs_island_stop, int)                            \
-  X("max_contacts_per_pair", max_con_pair, int) X("solver", solver, int) X("convex_pairs", convex_pairs, int) X("multiccd", multiccd, int)  \
-  X("sep_cache", sep_cache, int) X("manifold_cache", manifold_cache, int) X("pgs_dual_warmstart", pgs_dual_ws, int)                         \
-  X("", ls_iterations, int) X("", multi_serial, int) X("", ls_tolerance, float)
-
 // device memory owned by the context (freed in smj_destroy), zeroed
 template <class T>
 static int alloc_zeroed(smj_ctx* c, size_t count, T** out) {
@@ -429,26 +419,7 @@ int smj_bind(smj_ctx* c, int slot, void* p, long ld) {
   if (p && ld < c->num_envs) return fail(c, -1, "slot %d: ld %ld < num_envs %d", slot, ld, c->num_envs);
   c->slot_ptr[slot] = p;
   c->slot_ld[slot] = ld;
-  DevState& s = c->state;
-  switch (slot) {
-    case SMJ_SLOT_QPOS: s.qpos = (float*)p; break;
-    case SMJ_SLOT_QVEL: s.qvel = (float*)p; break;
-    case SMJ_SLOT_CTRL: s.ctrl = (float*)p; break;
-    case SMJ_SLOT_WARMSTART: s.warm = (float*)p; break;
-    case SMJ_SLOT_NSTEP: s.nstep = (int*)p; break;
-    case SMJ_SLOT_ACT_LENGTH: s.act_len = (float*)p; break;
-    case SMJ_SLOT_ACT_VELOCITY: s.act_vel = (float*)p; break;
-    case SMJ_SLOT_BASE_POSE: s.base = (float*)p; break;
-    case SMJ_SLOT_GYRO: s.gyro = (float*)p; break;
-    case SMJ_SLOT_ACCEL: s.accel = (float*)p; break;
-    case SMJ_SLOT_LIDAR: s.lidar = (float*)p; break;
-    case SMJ_SLOT_INFO: s.info = (int*)p; break;
-    case SMJ_SLOT_DEBUG: s.debug = (float*)p; break;
-    case SMJ_SLOT_PROF: s.prof = (float*)p; break;
-    case SMJ_SLOT_XPOSE: s.xpose = (float*)p; break;
-    case SMJ_SLOT_BASECTL: s.bctl = (float*)p; break;
-    case SMJ_SLOT_CONTACTS: break;   // env-major, its own leading dimension; handed to the kernel only by a call that reads it (smj_step)
-  }
+  smj_bind_slot(c->state, slot, p);   // (false for SMJ_SLOT_CONTACTS alone: kept in slot_ptr until a call reads it)
   return 0;
 }
 
@@ -714,10 +685,7 @@ int smj_set_option(smj_ctx* c, const char* name, double v) {
     const int n = (int)(v < 0 ? -v : v);
     c->pollers = n > 256 ? 256 : n;
   }
-#define X(opt, field, type) else if ((opt)[0] && !strcmp(name, opt)) m.field = (type)v;
-  SMJ_SOLVER_OPTIONS(X)   // the solver options of DevModel, by the list smj_step copies onto the escalation model
-#undef X
-  else return fail(c, -1, "unknown option '%s'", name);
+  else if (!smj_set_solver_option(m, name, v)) return fail(c, -1, "unknown option '%s'", name);   // the solver options of DevModel, by the list smj_step copies onto the escalation model
   return 0;
 }
 

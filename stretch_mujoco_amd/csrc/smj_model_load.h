@@ -10,7 +10,63 @@
 #include <string>
 #include <vector>
 
+#include "../../include/smj.h"
 #include "smj_model.h"
+
+// The solver options that live in DevModel: (option name of smj_set_option or "" for none, field, type).  smj_set_solver_option sets a
+// named one (smj_set_option on the primary model; the lane emulator), smj_step copies ALL of them onto the escalation model -- one list,
+// so the two kernels, and the emulator that checks them, cannot run with different options.
+// NOT here: row_limit ("primary_rows"): the escalation target keeps its full capacity.
+#define SMJ_SOLVER_OPTIONS(X)                                                                                                             \
+  X("iterations", iterations, int) X("tolerance", tolerance, float) X("warmstart", warmstart, int) X("pgs_fixed_iter", pgs_fixed_iter, int) \
+  X("qcqp_exact", qcqp_exact, int) X("grad_noise", grad_noise, float) X("pgs_island_stop", pgs_island_stop, int)                            \
+  X("max_contacts_per_pair", max_con_pair, int) X("solver", solver, int) X("convex_pairs", convex_pairs, int) X("multiccd", multiccd, int)  \
+  X("sep_cache", sep_cache, int) X("manifold_cache", manifold_cache, int) X("pgs_dual_warmstart", pgs_dual_ws, int)                         \
+  X("", ls_iterations, int) X("", multi_serial, int) X("", ls_tolerance, float)
+static inline bool smj_set_solver_option(DevModel& m, const char* name, double v) {   // false: the list has no option of that name
+#define X(opt, field, type) if ((opt)[0] && !strcmp(name, opt)) { m.field = (type)v; return true; }
+  SMJ_SOLVER_OPTIONS(X)
+#undef X
+  return false;
+}
+
+// Binds a batch-major slot of DevState by its SMJ_SLOT_* number (include/smj.h).  false: not one of them -- SMJ_SLOT_CONTACTS is
+// env-major with its own leading dimension, and is handed to the kernel only by a call that reads it (smj_step).
+static inline bool smj_bind_slot(DevState& s, int slot, void* p) {
+  switch (slot) {
+    case SMJ_SLOT_QPOS: s.qpos = (float*)p; break;
+    case SMJ_SLOT_QVEL: s.qvel = (float*)p; break;
+    case SMJ_SLOT_CTRL: s.ctrl = (float*)p; break;
+    case SMJ_SLOT_WARMSTART: s.warm = (float*)p; break;
+    case SMJ_SLOT_NSTEP: s.nstep = (int*)p; break;
+    case SMJ_SLOT_ACT_LENGTH: s.act_len = (float*)p; break;
+    case SMJ_SLOT_ACT_VELOCITY: s.act_vel = (float*)p; break;
+    case SMJ_SLOT_BASE_POSE: s.base = (float*)p; break;
+    case SMJ_SLOT_GYRO: s.gyro = (float*)p; break;
+    case SMJ_SLOT_ACCEL: s.accel = (float*)p; break;
+    case SMJ_SLOT_LIDAR: s.lidar = (float*)p; break;
+    case SMJ_SLOT_INFO: s.info = (int*)p; break;
+    case SMJ_SLOT_DEBUG: s.debug = (float*)p; break;
+    case SMJ_SLOT_PROF: s.prof = (float*)p; break;
+    case SMJ_SLOT_XPOSE: s.xpose = (float*)p; break;
+    case SMJ_SLOT_BASECTL: s.bctl = (float*)p; break;
+    default: return false;
+  }
+  return true;
+}
+
+// Which of `caps` (the kernel variants available to the caller, smallest first) runs a model of m's dimensions: the first one it fits,
+// -1 if none.  hint > 0 (k_capacity_hint of the model compiler, model_fuse.prepare_for_kernels: a contact-rich scene) skips the
+// standard variant -- tall if the model fits it, else big -- and comes back to it last (a satellite model has its own builds).
+static inline int smj_pick_variant(const DevModel& m, int hint, const SmjCaps* caps, int ncaps) {
+  const int first = (hint > 0 && ncaps > 1) ? 1 : 0;
+  for (int k = 0; k < ncaps; k++) {
+    const SmjCaps& c = caps[(first + k) % ncaps];
+    if ((m.nsat > 0) == (c.nsat > 0) && m.nsat <= c.nsat && m.nv <= (c.nvs ? c.nvs : c.nvp) && m.nbody <= c.nbp && m.nq <= c.nvp + 8 &&
+        m.nldl <= c.nent * 64) return (first + k) % ncaps;
+  }
+  return -1;
+}
 
 struct SmjBlobEntry {
   char name[48];
@@ -292,20 +348,12 @@ int smj_load_model(const void* blob, size_t nbytes, DevModel& m, Up& up, std::st
   }
   m.row_limit = 0; m.pgs_cap = 0; m.warmstart = 1; m.pgs_fixed_iter = 0; m.qcqp_exact = 0; m.grad_noise = 4e-6f; m.pgs_island_stop = 1; m.pgs_dual_ws = 1; m.max_con_pair = 4; m.solver = 0; m.convex_pairs = 1; m.multiccd = 1; m.sep_cache = getenv("SMJ_NO_SEPCACHE") ? 0 : 1; m.manifold_cache = (getenv("SMJ_NO_MCACHE") || m.nv_all <= 32) ? 0 : 1;   /* pays where free objects rest; a robot alone (<= 32 dofs) has no resting convex pair and the lookup cost the headline 1 % */ m.multi_serial = 0; m.ls_iterations = 50; m.ls_tolerance = 0.01f;
   char buf[256];
-  int pick = -1, first = 0;
-  {   // optional hint of the model compiler: contact-rich scene, start at the big variant (model_fuse.prepare_for_kernels)
+  int hint = 0;
+  {   // optional hint of the model compiler: contact-rich scene (smj_pick_variant)
     const SmjBlobEntry* e = b.find("k_capacity_hint");
-    int hint = 0;
     if (e && e->dtype == 1 && e->nbytes >= 4) memcpy(&hint, b.p + e->offset, 4);
-    if (hint > 0 && ncaps > 1) first = 1;   // skip the standard variant: tall if the model fits it, else big
   }
-  for (int v = first; v < ncaps && pick < 0; v++)
-    if ((m.nsat > 0) == (caps[v].nsat > 0) && m.nsat <= caps[v].nsat &&
-        m.nv <= (caps[v].nvs ? caps[v].nvs : caps[v].nvp) && m.nbody <= caps[v].nbp && m.nq <= caps[v].nvp + 8 && m.nldl <= caps[v].nent * 64) pick = v;
-  if (pick < 0 && first > 0)   // (the hint skips the standard variant; a satellite model has its own builds)
-    for (int v = 0; v < first && pick < 0; v++)
-      if ((m.nsat > 0) == (caps[v].nsat > 0) && m.nsat <= caps[v].nsat &&
-          m.nv <= (caps[v].nvs ? caps[v].nvs : caps[v].nvp) && m.nbody <= caps[v].nbp && m.nq <= caps[v].nvp + 8 && m.nldl <= caps[v].nent * 64) pick = v;
+  const int pick = smj_pick_variant(m, hint, caps, ncaps);
   if (pick < 0 || m.nu > 16) {
     const SmjCaps& c = caps[ncaps - 1];
     snprintf(buf, sizeof buf, "model exceeds kernel capacity (nv %d<=%d, nbody %d<=%d, nq %d<=%d, nu %d<=16, mass-matrix entries %d<=%d, satellites %d)",

@@ -1,58 +1,92 @@
-"""TEST INFRASTRUCTURE ONLY -- ctypes wrapper of tests/emul/libsmj_emul.so (CPU lane emulator of the HIP kernel)."""
+"""TEST INFRASTRUCTURE ONLY -- ctypes wrapper of tests/emul/libsmj_emul_<tag>.so (CPU lane emulator of the HIP kernel, one library per
+build tag of csrc/smj_builds.h).  Slots, variants, their builds and hand-over targets and the choice of a variant are asked of the
+library's own tables through the emulator (smj_emul.cpp); none is restated here."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import subprocess
 
 import numpy as np
 
+from stretch_mujoco_amd.lib import CONTACT_WORDS, SLOT
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = {}
 
-SLOTS = dict(qpos=0, qvel=1, ctrl=2, warm=3, nstep=4, act_len=5, act_vel=6, base=7, gyro=8, accel=9, lidar=10, info=11, debug=12, bctl=15)
+# buffer of Emul -> slot of emul_bind (SMJ_SLOT_*, include/smj.h)
+SLOTS = dict(qpos=SLOT["QPOS"], qvel=SLOT["QVEL"], ctrl=SLOT["CTRL"], warm=SLOT["WARMSTART"], nstep=SLOT["NSTEP"], act_len=SLOT["ACT_LENGTH"],
+             act_vel=SLOT["ACT_VELOCITY"], base=SLOT["BASE_POSE"], gyro=SLOT["GYRO"], accel=SLOT["ACCEL"], lidar=SLOT["LIDAR"], info=SLOT["INFO"],
+             debug=SLOT["DEBUG"], bctl=SLOT["BASECTL"])
+
+
+def _load(name: str, tag: str):
+    """libsmj_emul_<tag>.so, or what SMJ_EMUL_LIB_<NAME> names (an experimental build of that variant, tools only)."""
+    if name not in _LIB:
+        so = "libsmj_emul_%s.so" % tag
+        subprocess.check_call(["make", "-C", _HERE, "-s", so])
+        L = ctypes.CDLL(os.environ.get("SMJ_EMUL_LIB_" + name.upper()) or os.path.join(_HERE, so))
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.emul_create.restype = vp
+        L.emul_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ci]
+        L.emul_bind.argtypes = [vp, ci, vp, ctypes.c_long]
+        L.emul_bind_contacts.argtypes = [vp, vp, ci]
+        L.emul_step.argtypes = [vp, ci, ctypes.c_uint]
+        L.emul_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_double]
+        L.emul_clear_caches.argtypes = [vp]
+        L.emul_destroy.argtypes = [vp]
+        L.emul_caps.argtypes = [vp]
+        L.emul_pick_variant.argtypes = [ctypes.c_char_p, ctypes.c_size_t, vp, ci]
+        for f in ("emul_variant_name", "emul_variant_tag", "emul_variant_escalation"):
+            getattr(L, f).restype = ctypes.c_char_p
+        # event counters of the kernel source, per library and process: tests read differences
+        for f in ("emul_sep_skips", "emul_ext_steps", "emul_mc_hits", "emul_isl_total", "emul_isl_swept"):
+            getattr(L, f).restype = ctypes.c_long
+        _LIB[name] = L
+    return _LIB[name]
+
+
+@functools.lru_cache(None)
+def variants() -> tuple:
+    """The rows of csrc/smj_variants.h: (name, tag of the Newton build, tag of the hand-over target or None)."""
+    L = _load("standard", "step")   # (the table is the same in every library; this one bootstraps the names)
+    dec = lambda b: b.decode() if b is not None else None
+    return tuple((dec(L.emul_variant_name(v)), dec(L.emul_variant_tag(v)), dec(L.emul_variant_escalation(v))) for v in range(L.emul_nvariants()))
 
 
 def lib(variant: str = "standard"):
-    big = variant   # cache key
-    if big not in _LIB:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-        L = ctypes.CDLL(os.environ.get("SMJ_EMUL_LIB_" + variant.upper()) or os.path.join(_HERE, {"standard": "libsmj_emul.so", "tall": "libsmj_emul_tall.so", "mid": "libsmj_emul_mid.so", "big": "libsmj_emul_big.so", "big38": "libsmj_emul_big38.so", "big50": "libsmj_emul_big50.so", "poison": "libsmj_emul_poison.so", "sat": "libsmj_emul_sat.so", "sat32": "libsmj_emul_sat32.so"}[variant]))   # (SMJ_EMUL_LIB_<VARIANT>: an experimental build of that variant, tools only)
-        L.emul_create.restype = ctypes.c_void_p
-        L.emul_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
-        L.emul_bind.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
-        L.emul_step.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint]
-        L.emul_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double]
-        L.emul_destroy.argtypes = [ctypes.c_void_p]
-        _LIB[big] = L
-    return _LIB[big]
+    """A variant's library is the one of its Newton build ("standard": step); any other name is a build tag itself ("tall", "poison")."""
+    return _load(variant, {name: tag for name, tag, _ in variants()}.get(variant, variant))
+
+
+def escalation(variant: str):
+    """The variant the device hands a step to that runs out of rows / contacts in `variant`; None: it has none."""
+    return {name: esc for name, _, esc in variants()}.get(variant)
+
+
+def default_variant(blob: bytes) -> str:
+    """The variant smj_create starts the model on: the loader's own choice among the capacities of the table's rows."""
+    rows = variants()
+    caps = (ctypes.c_int * 7 * len(rows))()   # SmjCaps per row (csrc/smj_builds.h)
+    for v, (name, _, _) in enumerate(rows):
+        lib(name).emul_caps(caps[v])
+    v = lib().emul_pick_variant(blob, len(blob), caps, len(rows))
+    if v < 0:
+        raise ValueError("no kernel variant takes this model")
+    return rows[v][0]
 
 
 class Emul:
-    def __init__(self, blob: bytes, dims: dict, num_envs: int = 1, debug: bool = True, big: bool | None = None, variant: str | None = None):
-        """variant: "standard" (32 dofs / 80 rows / 16 contacts), "tall" (32 / 160 / 48), "mid" (32 / 128 / 44: the build of the tall
-        variant that smj_create runs as the primary kernel; the emulator has no escalation, so the default stays "tall") or "big"
-        (64 / 160 / 48); default: chosen
-        like smj_create does, by the model's size and the blob's capacity hint.  `big=True` is shorthand for variant="big"."""
+    def __init__(self, blob: bytes, dims: dict, num_envs: int = 1, debug: bool = True, variant: str | None = None):
+        """variant: a row of csrc/smj_variants.h ("standard", "mid", "big38", "big50", "big", "sat", "sat32") or a build tag ("tall",
+        "poison"); default: the one smj_create starts the model on, by the model's size and the blob's capacity hint."""
         if variant is None:
-            import stretch_mujoco_amd.model_blob as mb0
-
-            ns = mb0.loads(blob).get("k_nsat")
-            if ns is not None and int(np.asarray(ns).ravel()[0]) > 0:
-                variant = "sat" if int(np.asarray(ns).ravel()[0]) <= 16 else "sat32"
-        if variant is None:
-            if big or dims["nv"] > 32:   # the big variant is built for 38 / 50 / 64 dof columns (smj_model.h); big=True with a small model: 64
-                variant = "big38" if 32 < dims["nv"] <= 38 else "big50" if 38 < dims["nv"] <= 50 else "big"
-            else:
-                import stretch_mujoco_amd.model_blob as mb
-
-                hint = mb.loads(blob).get("k_capacity_hint")
-                variant = "tall" if hint is not None and int(np.asarray(hint).ravel()[0]) > 0 else "standard"
+            variant = default_variant(blob)
+            variant = "tall" if variant == "mid" else variant   # the one difference from smj_create: the emulator has no escalation of its own, so it runs `mid`'s hand-over target
         self.variant = variant
-        self.big = variant.startswith("big")
         self.L = lib(variant)
-        self.nvp, self.ncon_max = self.L.emul_nvp(), self.L.emul_ncon_max()
-        self.nsat_max = {"sat": 16, "sat32": 32}.get(variant, 0)
+        self.nvp, self.ncon_max, self.nsat_max = self.L.emul_nvp(), self.L.emul_ncon_max(), self.L.emul_nsat_max()
         self.B = B = num_envs
         self.c = self.L.emul_create(blob, len(blob), B)
         if not self.c:
@@ -67,17 +101,23 @@ class Emul:
         if debug:
             self.buf["debug"] = np.zeros((self.L.emul_debug_floats(), B), f)
         for k, a in self.buf.items():
-            self.L.emul_bind(self.c, SLOTS[k], a.ctypes.data_as(ctypes.c_void_p), B)
+            assert self.L.emul_bind(self.c, SLOTS[k], a.ctypes.data_as(ctypes.c_void_p), B) == 0
         # PGS: the emulator starts the sweeps the way MuJoCo does unless a test asks for the kernels' default (a second start from the
         # previous step's forces, option pgs_dual_warmstart = 1) -- most PGS tests compare iterate for iterate with the unmodified oracle
         self.set_option("pgs_dual_warmstart", 0)
+
+    def bind_contacts(self, cap: int):
+        """The contact-readout slot (SMJ_SLOT_CONTACTS): self.rec, env-major [B, cap, CONTACT_WORDS], written by a step with
+        lib.READ_CONTACTS; never-written words stay NaN."""
+        assert self.L.emul_contact_words() == CONTACT_WORDS
+        self.rec = np.full((self.B, cap, CONTACT_WORDS), np.nan, np.float32)
+        assert self.L.emul_bind_contacts(self.c, self.rec.ctypes.data_as(ctypes.c_void_p), cap) == 0
 
     def set_option(self, name, v):
         assert self.L.emul_set_option(self.c, name.encode(), float(v)) == 0
 
     def clear_caches(self):
         """What smj_reset drops beside the state: kept manifolds, separating directions, the PGS second start."""
-        self.L.emul_clear_caches.argtypes = [ctypes.c_void_p]
         self.L.emul_clear_caches(self.c)
 
     def set_poison(self, byte):
@@ -86,6 +126,10 @@ class Emul:
 
     def step(self, n=1, read_flags=0):
         self.L.emul_step(self.c, n, read_flags)
+
+    def close(self):
+        self.L.emul_destroy(self.c)
+        self.c = None
 
     def __getattr__(self, k):
         if k in self.__dict__.get("buf", {}):

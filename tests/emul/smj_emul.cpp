@@ -4,6 +4,10 @@
 // loop over 64 lanes and cross-lane ops act on arrays, in fp32, with the same operation order as the GPU
 // code.  It exists so that the kernel LOGIC can be checked against the fp64 oracle on a machine without a
 // GPU (`pytest -m "not gpu"`).  It is never linked into libsmj.so and nothing in stretch_mujoco_amd/ loads it.
+//
+// One library per build of the table in csrc/smj_builds.h: libsmj_emul_<tag>.so is this file with -DSMJ_BUILD_TAG=<tag> (Makefile) and
+// takes that build's capacities.  Options, slots, the variant table and the choice of a variant are the library's own code and
+// tables (csrc/smj_model_load.h, csrc/smj_variants.h, include/smj.h), exported below for tests/emul/emul.py -- nothing is restated here.
 #define SMJ_EMUL 1
 #include <stdlib.h>
 #include <string.h>
@@ -13,6 +17,7 @@
 
 #include "../../stretch_mujoco_amd/csrc/smj_model_load.h"
 #include "../../stretch_mujoco_amd/csrc/smj_step_impl.h"
+#include "../../stretch_mujoco_amd/csrc/smj_variants.h"
 
 struct HostUploader {
   std::vector<void*>* keep;
@@ -40,7 +45,7 @@ extern "C" {
 emul_ctx* emul_create(const void* blob, size_t nbytes, int num_envs) {
   emul_ctx* c = new emul_ctx();
   HostUploader up{&c->keep};
-  const SmjCaps caps{NVP, NBP, NENT, NEFC, NCON, NVS, NSAT};   // this build's variant (Makefile: -DSMJ_BIG for libsmj_emul_big.so)
+  const SmjCaps caps{NVP, NBP, NENT, NEFC, NCON, NVS, NSAT};   // this build's capacities (Makefile: -DSMJ_BUILD_TAG=<tag>)
   int chosen = 0;
   if (smj_load_model(blob, nbytes, c->m, up, c->err, &caps, 1, &chosen)) {
     fprintf(stderr, "emul_create: %s\n", c->err.c_str());
@@ -69,49 +74,25 @@ void emul_destroy(emul_ctx* c) {
   for (void* p : c->keep) free(p);
   delete c;
 }
-// same slot numbering as include/smj.h
-int emul_bind(emul_ctx* c, int slot, void* p, long ld) {
-  DevState& s = c->s;
-  s.ld = ld;
-  switch (slot) {
-    case 0: s.qpos = (float*)p; break;
-    case 1: s.qvel = (float*)p; break;
-    case 2: s.ctrl = (float*)p; break;
-    case 3: s.warm = (float*)p; break;
-    case 4: s.nstep = (int*)p; break;
-    case 5: s.act_len = (float*)p; break;
-    case 6: s.act_vel = (float*)p; break;
-    case 7: s.base = (float*)p; break;
-    case 8: s.gyro = (float*)p; break;
-    case 9: s.accel = (float*)p; break;
-    case 10: s.lidar = (float*)p; break;
-    case 11: s.info = (int*)p; break;
-    case 12: s.debug = (float*)p; break;
-    case 13: s.prof = (float*)p; break;
-    case 14: s.xpose = (float*)p; break;
-    case 15: s.bctl = (float*)p; break;
-    default: return -1;
-  }
+int emul_bind(emul_ctx* c, int slot, void* p, long ld) {   // slot: SMJ_SLOT_* (include/smj.h)
+  c->s.ld = ld;
+  return smj_bind_slot(c->s, slot, p) ? 0 : -1;
+}
+// the contact-readout slot (SMJ_SLOT_CONTACTS): env-major records [B][cap][SMJ_CR_WORDS], cap >= the build's NCON
+int emul_bind_contacts(emul_ctx* c, void* p, int cap) {
+  if (p && cap < NCON) return -1;
+  c->s.contacts = (float*)p;
+  c->s.con_cap = cap;
   return 0;
 }
+int emul_contact_words() { return SMJ_CR_WORDS; }
 int emul_set_option(emul_ctx* c, const char* name, double v) {
   DevModel& m = c->m;
-  if (!strcmp(name, "iterations")) m.iterations = (int)v;
-  else if (!strcmp(name, "tolerance")) m.tolerance = (float)v;
-  else if (!strcmp(name, "warmstart")) m.warmstart = (int)v;
-  else if (!strcmp(name, "pgs_fixed_iter")) m.pgs_fixed_iter = (int)v;
-  else if (!strcmp(name, "qcqp_exact")) m.qcqp_exact = (int)v;
-  else if (!strcmp(name, "grad_noise")) m.grad_noise = (float)v;
-  else if (!strcmp(name, "pgs_island_stop")) m.pgs_island_stop = (int)v;
-  else if (!strcmp(name, "pgs_cap")) m.pgs_cap = (int)v;   // what smj_step sets for a PGS launch without dynamic LDS (smj_step_tu.h)
-  else if (!strcmp(name, "max_contacts_per_pair")) m.max_con_pair = (int)v;
-  else if (!strcmp(name, "solver")) m.solver = (int)v;
-  else if (!strcmp(name, "convex_pairs")) m.convex_pairs = (int)v;
-  else if (!strcmp(name, "multiccd")) m.multiccd = (int)v;
+  if (smj_set_solver_option(m, name, v)) return 0;   // the library's list (SMJ_SOLVER_OPTIONS)
+  // emulator only: two fields the library never takes by name.  pgs_cap is what smj_step_tu.h sets itself for a PGS launch without
+  // dynamic LDS; multi_serial keeps the serial multiccd search as the comparator of the batched one.
+  if (!strcmp(name, "pgs_cap")) m.pgs_cap = (int)v;
   else if (!strcmp(name, "multi_serial")) m.multi_serial = (int)v;
-  else if (!strcmp(name, "sep_cache")) m.sep_cache = (int)v;
-  else if (!strcmp(name, "manifold_cache")) m.manifold_cache = (int)v;
-  else if (!strcmp(name, "pgs_dual_warmstart")) m.pgs_dual_ws = (int)v;
   else return -1;
   return 0;
 }
@@ -137,4 +118,34 @@ int emul_nvp() { return NVP; }
 int emul_lds_bytes() { return (int)sizeof(Smem); }
 int emul_ncon_max() { return NCON; }
 int emul_nefc_max() { return NEFC; }
+int emul_nsat_max() { return NSAT; }
+void emul_caps(SmjCaps* out) { *out = SmjCaps{NVP, NBP, NENT, NEFC, NCON, NVS, NSAT}; }
+
+// ---- the table of variants (csrc/smj_variants.h), the same in every library: row v's name, the tag of its Newton build (whose
+// capacities are the variant's), the tag of the build a step beyond them is handed to (null: none)
+static const char* const build_tags[SMJ_B_COUNT] = {
+#define X(tag) #tag,
+    SMJ_BUILDS(X)
+#undef X
+};
+int emul_nvariants() { return SMJ_NVARIANTS; }
+const char* emul_variant_name(int v) { return smj_variants[v].name; }
+const char* emul_variant_tag(int v) { return build_tags[smj_variants[v].newton]; }
+const char* emul_variant_escalation(int v) {
+  const SmjVariant& V = smj_variants[v];
+  return V.esc_variant != SMJ_NO_VARIANT ? emul_variant_tag(V.esc_variant) : V.esc_build != SMJ_NO_BUILD ? build_tags[V.esc_build] : nullptr;
+}
+// The row smj_create starts a model on: smj_load_model's choice (smj_pick_variant) among `caps`, the capacities of the table's rows in
+// order (each from its own library's emul_caps).  -1: the loader refuses the model.
+int emul_pick_variant(const void* blob, size_t nbytes, const SmjCaps* caps, int ncaps) {
+  DevModel m{};
+  std::vector<void*> keep;
+  HostUploader up{&keep};
+  std::string err;
+  int chosen = -1;
+  const int rc = smj_load_model(blob, nbytes, m, up, err, caps, ncaps, &chosen);
+  for (void* p : keep) free(p);
+  if (rc) fprintf(stderr, "emul_pick_variant: %s\n", err.c_str());
+  return rc ? -1 : chosen;
+}
 }

@@ -449,16 +449,16 @@ class EmulBackend:
     """The kernel source through the CPU lane emulator (tests/emul).  The emulator has no escalation of its own; for single steps
     from an uploaded state (the state-synchronised protocol) this backend does what smj_step does on the device: an env whose step
     ran out of constraint rows / contacts in the primary variant is stepped again, from the same state, by the variant the
-    device hands it to (standard / mid -> tall, big38 / big50 -> big, sat -> sat32), and that result is the one reported."""
-    ESC = {"standard": "tall", "mid": "tall", "big38": "big", "big50": "big", "sat": "sat32"}
+    device hands it to (the escalation columns of csrc/smj_variants.h, through emul.escalation), and that result is the one reported."""
 
     def __init__(self, blob, B, solver=2, variant=None):
-        from emul.emul import Emul
+        from emul.emul import Emul, escalation
 
         o = Oracle(blob)
         self.dims = dict(nq=o.dim("nq"), nv=o.dim("nv"), nu=o.dim("nu"), nlidar=360)
         self.blob, self.B = blob, B
         self.e = Emul(blob, self.dims, num_envs=B, debug=True, variant=variant)   # variant as smj_create picks it
+        self.esc = escalation(self.e.variant)   # None: the variant hands nothing over
         self._opts = {}
         orig = self.e.set_option
 
@@ -493,7 +493,7 @@ class EmulBackend:
     def step(self, n):
         self.handed = []
         st, self._state = self._state, None
-        if n != 1 or st is None or self.e.variant not in self.ESC:
+        if n != 1 or st is None or self.esc is None:
             self.e.step(n)
             return
         ctrl0 = self.e.ctrl.copy()
@@ -506,7 +506,7 @@ class EmulBackend:
             from stretch_mujoco_amd.lib import debug_layout
 
             if self.x is None:
-                self.x = Emul(self.blob, self.dims, num_envs=self.B, debug=True, variant=self.ESC[self.e.variant])
+                self.x = Emul(self.blob, self.dims, num_envs=self.B, debug=True, variant=self.esc)
                 self.xD = debug_layout(self.x.nvp, self.x.ncon_max, self.x.nsat_max)
             for k, v in self._opts.items():
                 self.x.set_option(k, v)

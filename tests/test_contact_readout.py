@@ -1,22 +1,20 @@
 """Contact readout (SMJ_SLOT_CONTACTS / StretchBatchSimulator.pull_contact_data) on the CPU: the ABI constants, the decoding of
-hand-made records and the helpers, and the kernel's writer through the lane emulator (tests/emul_contacts: tests/emul's
-emulator plus the slot) against the debug dump and the fp64 oracle on identical contacts.  The `-m gpu` twin is
+hand-made records and the helpers, and the kernel's writer through the lane emulator (tests/emul, Emul.bind_contacts)
+against the debug dump and the fp64 oracle on identical contacts.  The `-m gpu` twin is
 tests/test_gpu_contacts.py."""
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import MIX_CTRL, MODELS, ROOT, home_qpos
+from emul.emul import Emul
 from oracle.oracle import Oracle
 from stretch_mujoco_amd import StretchBatchSimulator, lib
 from stretch_mujoco_amd.datamodels import StatusStretchContacts
 
-HARNESS = os.path.join(ROOT, "tests", "emul_contacts")
 W = lib.CONTACT_WORDS
 
 
@@ -120,55 +118,6 @@ def test_body_names_through_geom_origbody():
 
 
 # ---------------------------------------------------------------------------------------------- kernel logic on the emulator
-_LIBS = {}
-
-
-def _harness(variant):
-    if variant not in _LIBS:
-        subprocess.check_call(["make", "-C", HARNESS, "-s"])
-        L = ctypes.CDLL(os.path.join(HARNESS, {"standard": "libsmj_emul_contacts.so", "sat": "libsmj_emul_contacts_sat.so"}[variant]))
-        vp = ctypes.c_void_p
-        L.emul_create.restype = vp
-        L.emul_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
-        L.emul_bind.argtypes = [vp, ctypes.c_int, vp, ctypes.c_long]
-        L.emul_bind_contacts.argtypes = [vp, vp, ctypes.c_int]
-        L.emul_step.argtypes = [vp, ctypes.c_int, ctypes.c_uint]
-        L.emul_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_double]
-        L.emul_destroy.argtypes = [vp]
-        _LIBS[variant] = L
-    return _LIBS[variant]
-
-
-class _Emul:
-    """One env of the emulator with every slot bound (tests/emul/emul.py's layout) and the contact records."""
-
-    SLOTS = dict(qpos=0, qvel=1, ctrl=2, warm=3, nstep=4, act_len=5, act_vel=6, base=7, gyro=8, accel=9, lidar=10, info=11, debug=12, bctl=15)
-
-    def __init__(self, blob, o, variant):
-        self.L = L = _harness(variant)
-        self.c = L.emul_create(blob, len(blob), 1)
-        assert self.c
-        nq, nv, nu = o.dim("nq"), o.dim("nv"), o.dim("nu")
-        f = np.float32
-        self.ncon_max = L.emul_ncon_max()
-        self.buf = dict(qpos=np.zeros((nq, 1), f), qvel=np.zeros((nv, 1), f), ctrl=np.zeros((max(nu, 1), 1), f), warm=np.zeros((nv, 1), f),
-                        nstep=np.zeros(1, np.int32), act_len=np.zeros((max(nu, 1), 1), f), act_vel=np.zeros((max(nu, 1), 1), f),
-                        base=np.zeros((3, 1), f), gyro=np.zeros((3, 1), f), accel=np.zeros((3, 1), f), lidar=np.zeros((360, 1), f),
-                        info=np.zeros((4, 1), np.int32), bctl=np.zeros((8, 1), f), debug=np.zeros((L.emul_debug_floats(), 1), f))
-        for k, a in self.buf.items():
-            L.emul_bind(self.c, self.SLOTS[k], a.ctypes.data_as(ctypes.c_void_p), 1)
-        self.cap = 64
-        self.rec = np.full((1, self.cap, W), np.nan, np.float32)   # never-written words stay NaN
-        assert L.emul_bind_contacts(self.c, self.rec.ctypes.data_as(ctypes.c_void_p), self.cap) == 0
-        L.emul_set_option(self.c, b"pgs_dual_warmstart", 0.0)
-
-    def step(self, n, flags):
-        self.L.emul_step(self.c, n, flags)
-
-    def close(self):
-        self.L.emul_destroy(self.c)
-
-
 def _settled(blob, solver, steps=300):
     o = Oracle(blob)
     o.set_option("solver", solver)
@@ -190,7 +139,8 @@ def _oracle_contacts(o):
 def test_emulated_records_match_dump_and_oracle(scene, variant, solver):
     blob = open(os.path.join(MODELS, scene + ".smjb"), "rb").read()
     o = _settled(blob, solver)
-    e = _Emul(blob, o, variant)
+    e = Emul(blob, dict(nq=o.dim("nq"), nv=o.dim("nv"), nu=o.dim("nu"), nlidar=360), num_envs=1, variant=variant)
+    e.bind_contacts(64)   # never-written words stay NaN
     try:
         e.buf["qpos"][:, 0] = o.arr("qpos"); e.buf["qvel"][:, 0] = o.arr("qvel"); e.buf["warm"][:, 0] = o.arr("qacc_warmstart")
         e.buf["ctrl"][: o.dim("nu"), 0] = o.arr("ctrl")

@@ -4,7 +4,6 @@ stay out of the pair table the kernels scan.  Everything here is the kernel sour
 emulator on the CPU, through libsmj.so on the GPU (`-m gpu`) -- on the reference's own scene.xml, the kitchen stand-in with four
 objects, the small kitchen export and the generated kitchen at Robocasa scale (tests/kitchen_robocasa_fixture.py:
 44 fixture bodies, 307 collision geoms, 8 articulated parts, 8 free objects).  TEST INFRASTRUCTURE (imports oracle/)."""
-import ctypes
 import os
 
 import numpy as np
@@ -161,7 +160,6 @@ def test_emul_dense_extension_and_manifold_cache_are_exercised():
     from emul.emul import lib
 
     L = lib("sat")
-    L.emul_ext_steps.restype = ctypes.c_long; L.emul_mc_hits.restype = ctypes.c_long
     e0, h0 = L.emul_ext_steps(), L.emul_mc_hits()
     be, rel, events = _sync("stretch_scene_sat", 4, 4)
     assert L.emul_ext_steps() - e0 > 20, "no step coupled a satellite to the robot"
@@ -198,7 +196,6 @@ def test_emul_kept_manifolds_ride_with_the_bodies_to_first_order():
     from emul.emul import lib
 
     L = lib("sat")
-    L.emul_mc_hits.restype = ctypes.c_long
     blob, model = _blob("stretch_kitchen_robocasa")
     be = rc.EmulBackend(blob, 1, variant="sat")
     orc = rc.settled_oracles(blob, 1, settle=300)

@@ -193,4 +193,5 @@ const char* smj_version(void);
 #ifdef __cplusplus
 }
 #endif
+#include "smj_pointcloud.h"   /* organised point clouds from the depth images: smj_depth_to_points */
 #endif

@@ -20,6 +20,7 @@
 #include "smj_bvh.h"
 #include "smj_meshlet.h"
 #include "smj_render.h"
+#include "smj_points.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -76,6 +77,7 @@ struct smj_ctx {
   struct Layer { int cam = -1, w = 0, h = 0; float fovy = 0; float* buf = nullptr; };
   std::vector<Layer> layers;
   float* depth_ws = nullptr;   // scratch of the depth renderer's per-env staging pass (allocated at the first render)   // internal [nbody*12][num_envs] body poses when the caller has not bound SMJ_SLOT_XPOSE
+  float* points_ws = nullptr;  // per-env transforms of smj_depth_to_points (allocated at the first call)
   void* slot_ptr[SMJ_SLOT_COUNT] = {};
   long slot_ld[SMJ_SLOT_COUNT] = {};
   // RCCL communicator of the env-sharded job (smj_comm_init); null in a single-GPU run
@@ -659,6 +661,34 @@ int smj_render_rgb(smj_ctx* c, int cam, int width, int height, float fovy_deg, v
   }
   smj_launch_rgb(c->render, c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, cam, width, height, fovy_deg,
                  (unsigned char*)rgb_dev, (int*)gid_dev, c->depth_ws, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_depth_to_points(smj_ctx* c, int cam, int width, int height, float fovy_deg, const void* depth_dev, int stride, int frame,
+                        void* points_dev, void* stream) {
+  if (!c) return -1;
+  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*): no cameras");
+  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
+  if (width < 1 || height < 1 || stride < 1 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / stride / field of view");
+  if (!depth_dev || !points_dev) return fail(c, -1, "null depth image / point buffer");
+  if (((uintptr_t)depth_dev | (uintptr_t)points_dev) & 3) return fail(c, -1, "depth image / point buffer not aligned to 4 bytes");
+  if (frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_CAMERA, SMJ_FRAME_WORLD or a body id)", frame);
+  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
+  const long long per_env = (long long)smj_points_grid(width, stride) * smj_points_grid(height, stride);
+  if (per_env > 0x7fffffffLL || per_env * c->num_envs > 0x7fffffffLL * 1024) return fail(c, -1, "point grid too large");
+  if (frame != SMJ_FRAME_CAMERA && !c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->points_ws) {
+    void* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, smj_points_workspace_bytes(c->num_envs)));
+    c->allocs.push_back(d);
+    c->points_ws = (float*)d;
+  }
+  const int kind = frame == SMJ_FRAME_CAMERA ? SMJ_PT_CAMERA : frame == SMJ_FRAME_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
+  smj_launch_points(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam,
+                    width, height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, (float*)points_dev,
+                    c->points_ws, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

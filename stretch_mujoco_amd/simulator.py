@@ -4,7 +4,8 @@ Reference: stretch_mujoco/stretch_mujoco_simulator.py:34-534 (client) + stretch_
 The server process, proxies, locks and the realtime sleep (mujoco_server.py:381-384) have no place in a batched
 throughput simulator: one Python object owns PyTorch-ROCm tensors (batch-major, [dim, B]) and drives the HIP
 library through the ctypes C-ABI (lib.py, include/smj.h).  New, without a reference counterpart: `step(n)`,
-`reset(env_ids)`, and with `contacts=True` the contact readout `pull_contact_data()`, `contact_force()`, `in_contact()`.
+`reset(env_ids)`, with `contacts=True` the contact readout `pull_contact_data()`, `contact_force()`, `in_contact()`, and the organised
+point clouds of the depth cameras, `pull_point_cloud()`.
 
 Ordering contract kept from `_ctrl_callback` (mujoco_server.py:450-463): commands issued between steps are
 folded into ctrl before the next physics step; status is the post-step readout.
@@ -139,6 +140,8 @@ class StretchBatchSimulator:
         if StretchSensors.base_lidar in self._sensors:
             self._read_flags |= _lib.READ_LIDAR
         self._depth = {}
+        self._depth_valid = set()   # depth cameras whose image has been rendered (pull_point_cloud(render=False) needs one)
+        self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
         self.xpose = torch.zeros(dims[D["NBODY"]] * 12, B, **f)
         _lib.check(L, ctx, L.smj_bind(ctx, S["XPOSE"], ctypes.c_void_p(self.xpose.data_ptr()), B), "smj_bind(XPOSE)")
@@ -293,10 +296,8 @@ class StretchBatchSimulator:
             st = cam.initial_camera_settings
             img = self._depth[cam]
             if cam.is_depth:
-                rc = self._L.smj_render_depth(self._ctx, names.index(cam.camera_name_in_mjcf), st.width, st.height,
-                                              float(st.field_of_view_vertical_in_degrees), cam.depth_limit,
-                                              ctypes.c_void_p(img.data_ptr()), self._stream())
-                _lib.check(self._L, self._ctx, rc, "smj_render_depth")
+                self._render_depth_into(cam, img)
+                self._depth_valid.add(cam)
             else:
                 rc = self._L.smj_render_rgb(self._ctx, names.index(cam.camera_name_in_mjcf), st.width, st.height,
                                             float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), None,
@@ -307,6 +308,70 @@ class StretchBatchSimulator:
             st = cam.initial_camera_settings
             setattr(out, attr, compute_K(st.field_of_view_vertical_in_degrees, st.sensor_resolution[0], st.sensor_resolution[1]))
         return out
+
+    def _render_depth_into(self, cam, img) -> None:
+        st = cam.initial_camera_settings
+        rc = self._L.smj_render_depth(self._ctx, self.names["camera"].index(cam.camera_name_in_mjcf), st.width, st.height,
+                                      float(st.field_of_view_vertical_in_degrees), cam.depth_limit,
+                                      ctypes.c_void_p(img.data_ptr()), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_render_depth")
+
+    @_require_connection
+    def pull_point_cloud(self, camera: StretchCameras, frame: str = "camera", stride: int = 1, render: bool = True,
+                         auto_rotate: bool = False) -> torch.Tensor:
+        """Organised point cloud [B, H', W', 3] (fp32 metres) of a depth camera of cameras_to_use, one fused pass over its depth
+        image (smj_depth_to_points, include/smj_pointcloud.h).  New, without a reference counterpart: users of the reference deproject
+        pull_camera_data() by hand -- and the cam_*_K fields do not fit the images (they follow get_camera_params: the sensor
+        resolution); utils.render_K is the matrix that does.
+
+        frame: "camera" -- the optical frame, x right, y down, z forward (OpenCV / ROS), of the image as rendered (for the d435i:
+        the sideways image, before get_camera_data turns it); "world"; or "base" -- the simulated base_link body frame, as
+        get_link_pose("base_link", simulated=True) places it.  stride = s keeps the pixels (s j, s i): H' = ceil(H / s),
+        W' = ceil(W / s).  Pixels without a depth (0: beyond the camera's depth_limit) are NaN rows.
+        render=True renders the depth first, into the image pull_camera_data() uses and with the camera's depth_limit;
+        render=False deprojects the image of the last pull_camera_data() / pull_point_cloud().
+        auto_rotate=True turns the GRID as get_camera_data turns the image (rot90(-1) over the grid axes for the d435i): a view,
+        the xyz values are untouched.  The tensor is simulator-owned and overwritten by the next call with the same (camera, stride)."""
+        if not isinstance(camera, StretchCameras) or not camera.is_depth or camera not in self._cameras:
+            raise ValueError(f"{camera} is not a depth camera of cameras_to_use")
+        if frame not in ("camera", "world", "base"):
+            raise ValueError('frame must be "camera", "world" or "base"')
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        st = camera.initial_camera_settings
+        img = self._depth[camera]
+        if render:
+            self._render_depth_into(camera, img)
+            self._depth_valid.add(camera)
+        elif camera not in self._depth_valid:
+            raise _lib.SmjError(f"render=False: {camera.name} has not been rendered yet (pull_camera_data() or pull_point_cloud() first)")
+        key = (camera, stride)
+        pts = self._points.get(key)
+        if pts is None:
+            pts = self._points[key] = torch.zeros(self.num_envs, -(-st.height // stride), -(-st.width // stride), 3,
+                                                  dtype=torch.float32, device=self.device)
+        offset = None
+        if frame == "base":
+            i = self.names["body"].index("base_link")
+            fr = int(self.model["link_fused"][i])      # the fused body base_link lives in, and its fixed pose there
+            rp = np.asarray(self.model["link_relpos"][i], np.float64)
+            Rl = self._quat_mat(self.model["link_relquat"][i], self.device)
+            if np.any(rp != 0) or not torch.equal(Rl, torch.eye(3, device=self.device)):
+                offset = (torch.tensor(rp, dtype=torch.float32, device=self.device), Rl)
+        else:
+            fr = _lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD
+        rc = self._L.smj_depth_to_points(self._ctx, self.names["camera"].index(camera.camera_name_in_mjcf), st.width, st.height,
+                                         float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), stride, fr,
+                                         ctypes.c_void_p(pts.data_ptr()), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_depth_to_points")
+        if offset is not None:
+            # base_link welded into a larger fused body (no shipped model does this): the constant link pose in that body, applied
+            # exactly -- p_link = R_l' (p_body - r_l) -- as a second pass over the cloud; NaN rows stay NaN
+            torch.matmul(pts - offset[0], offset[1], out=pts)
+        if auto_rotate and camera == StretchCameras.cam_d435i_depth:
+            return torch.rot90(pts, -1, (1, 2))
+        return pts
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

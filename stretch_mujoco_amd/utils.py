@@ -45,6 +45,27 @@ def compute_K(fovy: float, width: int, height: int) -> np.ndarray:
     return np.array(((f, 0, width / 2), (0, f, height / 2), (0, 0, 1)))
 
 
+def render_K(fovy: float, width: int, height: int, stride: int = 1) -> np.ndarray:
+    """The intrinsic matrix that fits an image rendered at `width` x `height` with vertical field of view `fovy` (degrees), and the
+    point clouds made from it (StretchBatchSimulator.pull_point_cloud): compute_K(fovy, width, height) read under the renderer's
+    pixel-centre convention -- pixel index u sits at image coordinate u + 0.5, so a point (x, y, z) of the optical frame (x right,
+    y down, z forward) lies in pixel (u, v) with K @ (x, y, z) / z = (u + 0.5, v + 0.5, 1).  (The cam_*_K fields of
+    pull_camera_data follow the reference instead: the sensor resolution, which is not the image's.)
+
+    stride = s > 1 gives the matrix of the subsampled grid of a point cloud: grid cell (i, j) -- row i, column j -- is image pixel
+    (u, v) = (s j, s i), the grid has ceil(height / s) rows and ceil(width / s) columns, and the returned matrix sends the cell's
+    point to (j + 0.5, i + 0.5, 1): focal length f / s, principal point ((c - 0.5) / s + 0.5).  With stride = 1 and a strided
+    cloud, the projection is the image coordinate (s j + 0.5, s i + 0.5) of the pixel the cell was taken from."""
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    K = compute_K(fovy, width, height)
+    if stride > 1:
+        K[0, 0] /= stride; K[1, 1] /= stride
+        K[0, 2] = (K[0, 2] - 0.5) / stride + 0.5
+        K[1, 2] = (K[1, 2] - 0.5) / stride + 0.5
+    return K
+
+
 def limit_depth_distance(depth_image_meters, max_depth: float):
     """Values strictly greater than max_depth become 0 (works for numpy arrays and torch tensors)."""
     try:

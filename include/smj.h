@@ -194,4 +194,5 @@ const char* smj_version(void);
 }
 #endif
 #include "smj_pointcloud.h"   /* organised point clouds from the depth images: smj_depth_to_points */
+#include "smj_heightmap.h"    /* egocentric height maps from the depth images: smj_depth_to_heightmap */
 #endif

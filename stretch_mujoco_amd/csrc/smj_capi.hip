@@ -21,6 +21,7 @@
 #include "smj_meshlet.h"
 #include "smj_render.h"
 #include "smj_points.h"
+#include "smj_hmap.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -689,6 +690,32 @@ int smj_depth_to_points(smj_ctx* c, int cam, int width, int height, float fovy_d
   smj_launch_points(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam,
                     width, height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, (float*)points_dev,
                     c->points_ws, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_depth_to_heightmap(smj_ctx* c, int cam, int width, int height, float fovy_deg, const void* depth_dev, int stride, int frame,
+                           float x0, float y0, float cell, int nx, int ny, float z_lo, float z_hi, int accumulate, void* zmax_dev,
+                           void* count_dev, void* stream) {
+  if (!c) return -1;
+  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*): no cameras");
+  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
+  if (width < 1 || height < 1 || stride < 1 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / stride / field of view");
+  if ((long long)width * height > 0x7fffffffLL) return fail(c, -1, "image too large");
+  if (nx < 1 || ny < 1 || (long long)nx * ny > SMJ_HMAP_MAX_CELLS) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, (int)SMJ_HMAP_MAX_CELLS);
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (!(z_lo <= z_hi)) return fail(c, -1, "bad height band (NaN, or z_lo > z_hi)");
+  if (!depth_dev || !zmax_dev) return fail(c, -1, "null depth image / height buffer");
+  if (((uintptr_t)depth_dev | (uintptr_t)zmax_dev | (uintptr_t)count_dev) & 3) return fail(c, -1, "depth image / height / count buffer not aligned to 4 bytes");
+  if (frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_CAMERA, SMJ_FRAME_WORLD or a body id)", frame);
+  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
+  if (frame != SMJ_FRAME_CAMERA && !c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int kind = frame == SMJ_FRAME_CAMERA ? SMJ_PT_CAMERA : frame == SMJ_FRAME_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
+  smj_launch_hmap(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam, width,
+                  height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, x0, y0, cell, nx, ny, z_lo, z_hi,
+                  accumulate != 0, (float*)zmax_dev, (int*)count_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -126,6 +126,20 @@ class StatusStretchCameras:  # status_stretch_camera.py:10-125 (depth only on th
 
 
 @dataclass
+class StatusStretchHeightMap:
+    """New, without a reference counterpart: the egocentric 2.5-D grid of pull_height_map() (smj_depth_to_heightmap).  Cell
+    (iy, ix) covers [origin[0] + ix cell, origin[0] + (ix + 1) cell) x [origin[1] + iy cell, origin[1] + (iy + 1) cell) of `frame`;
+    rows follow y.  Device tensors, simulator-owned, not synchronised to the host.  The map holds whatever the cameras see,
+    the robot's own arm included."""
+    time: Any
+    height: Any         # [B, ny, nx] float32: largest z of the cell's points inside z_range, NaN for a cell with none
+    count: Any          # [B, ny, nx] int32: number of those points
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "base", "world" or "camera"
+
+
+@dataclass
 class StatusStretchContacts:
     """New, without a reference counterpart (like `step` / `reset`): the contact list of every env's last physics step and its
     constraint forces -- what MuJoCo users read from MjData.contact and mj_contactForce after mj_step.  Every field is a device

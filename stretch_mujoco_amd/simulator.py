@@ -22,7 +22,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchJoints, StatusStretchSensors
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchHeightMap, StatusStretchJoints, StatusStretchSensors
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -141,6 +141,7 @@ class StretchBatchSimulator:
             self._read_flags |= _lib.READ_LIDAR
         self._depth = {}
         self._depth_valid = set()   # depth cameras whose image has been rendered (pull_point_cloud(render=False) needs one)
+        self._hmaps = {}            # (frame, (ny, nx)) -> the simulator-owned (height, count) of pull_height_map
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
         self.xpose = torch.zeros(dims[D["NBODY"]] * 12, B, **f)
@@ -372,6 +373,81 @@ class StretchBatchSimulator:
         if auto_rotate and camera == StretchCameras.cam_d435i_depth:
             return torch.rot90(pts, -1, (1, 2))
         return pts
+
+    @_require_connection
+    def pull_height_map(self, cameras: Optional[Sequence[StretchCameras]] = None, frame: str = "base", origin=(-1.6, -1.6),
+                        cell: float = 0.05, shape=(64, 64), z_range=(-float("inf"), float("inf")), stride: int = 1,
+                        render: bool = True) -> StatusStretchHeightMap:
+        """Egocentric 2.5-D grid around the robot, fused over depth cameras in one HIP pass per camera (smj_depth_to_heightmap,
+        include/smj_heightmap.h): per cell the largest z of the points that fall into it with z_range[0] <= z <= z_range[1]
+        (`height`, NaN where there is none) and their number (`count`).  New, without a reference counterpart.
+
+        cameras: depth cameras of cameras_to_use; None means all of them.  The first camera overwrites the map, the others
+        accumulate into it; max and count do not depend on the order.  frame: "base" (the simulated base_link body frame), "world"
+        or "camera" (the optical frame of each camera: meaningful for one camera).  Cell (iy, ix) covers origin + [ix, ix + 1) cell
+        in x and origin + [iy, iy + 1) cell in y; shape = (ny, nx), ny nx <= 65536.  stride = s keeps the pixels (s j, s i).
+        render as in pull_point_cloud: True renders each camera's depth first (with its depth_limit), False uses the image of the
+        last pull_camera_data() / pull_point_cloud() / pull_height_map().
+        The map includes the robot's own arm and gripper where a camera sees them: there is no self-filter.
+        The tensors are simulator-owned and overwritten by the next call with the same (frame, shape)."""
+        depth_cams = [c for c in self._cameras if c.is_depth]
+        cams = depth_cams if cameras is None else ([cameras] if isinstance(cameras, StretchCameras) else list(cameras))
+        if not cams:
+            raise ValueError("no depth camera in cameras_to_use")
+        for c in cams:
+            if not isinstance(c, StretchCameras) or c not in depth_cams:
+                raise ValueError(f"{c} is not a depth camera of cameras_to_use")
+        if frame not in ("camera", "world", "base"):
+            raise ValueError('frame must be "camera", "world" or "base"')
+        try:
+            ny, nx = (int(v) for v in shape)
+            x0, y0 = (float(v) for v in origin)
+            lo, hi = (float(v) for v in z_range)
+        except (TypeError, ValueError):
+            raise ValueError("shape = (ny, nx), origin = (x0, y0), z_range = (lo, hi)") from None
+        if ny < 1 or nx < 1 or ny * nx > 65536:
+            raise ValueError("shape: ny, nx >= 1 and ny * nx <= 65536")
+        cell = float(cell)
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        if not (np.isfinite(x0) and np.isfinite(y0)):
+            raise ValueError("origin must be finite")
+        if not lo <= hi:
+            raise ValueError("z_range: lo <= hi, neither NaN")
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        if frame == "base":
+            i = self.names["body"].index("base_link")
+            fr = int(self.model["link_fused"][i])
+            if np.any(np.asarray(self.model["link_relpos"][i], np.float64) != 0) or not torch.equal(
+                    self._quat_mat(self.model["link_relquat"][i], self.device), torch.eye(3, device=self.device)):
+                raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned map cannot be '
+                                 'corrected afterwards (use frame="world", or pull_point_cloud)')
+        else:
+            fr = _lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD
+        if not render:
+            for c in cams:
+                if c not in self._depth_valid:
+                    raise _lib.SmjError(f"render=False: {c.name} has not been rendered yet (pull_camera_data() or pull_point_cloud() first)")
+        key = (frame, (ny, nx))
+        bufs = self._hmaps.get(key)
+        if bufs is None:
+            bufs = self._hmaps[key] = (torch.full((self.num_envs, ny, nx), float("nan"), dtype=torch.float32, device=self.device),
+                                       torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device))
+        for k, c in enumerate(cams):
+            st = c.initial_camera_settings
+            img = self._depth[c]
+            if render:
+                self._render_depth_into(c, img)
+                self._depth_valid.add(c)
+            rc = self._L.smj_depth_to_heightmap(self._ctx, self.names["camera"].index(c.camera_name_in_mjcf), st.width, st.height,
+                                                float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), stride, fr,
+                                                x0, y0, cell, nx, ny, lo, hi, int(k > 0), ctypes.c_void_p(bufs[0].data_ptr()),
+                                                ctypes.c_void_p(bufs[1].data_ptr()), self._stream())
+            _lib.check(self._L, self._ctx, rc, "smj_depth_to_heightmap")
+        return StatusStretchHeightMap(time=self.nstep.to(torch.float64) * self.timestep, height=bufs[0], count=bufs[1], origin=(x0, y0),
+                                      cell=cell, frame=frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

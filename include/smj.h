@@ -195,4 +195,5 @@ const char* smj_version(void);
 #endif
 #include "smj_pointcloud.h"   /* organised point clouds from the depth images: smj_depth_to_points */
 #include "smj_heightmap.h"    /* egocentric height maps from the depth images: smj_depth_to_heightmap */
+#include "smj_occupancy.h"    /* 2-D occupancy grids from the lidar scan: smj_lidar_to_occupancy */
 #endif

@@ -22,6 +22,7 @@
 #include "smj_render.h"
 #include "smj_points.h"
 #include "smj_hmap.h"
+#include "smj_occ.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -716,6 +717,30 @@ int smj_depth_to_heightmap(smj_ctx* c, int cam, int width, int height, float fov
   smj_launch_hmap(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam, width,
                   height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, x0, y0, cell, nx, ny, z_lo, z_hi,
                   accumulate != 0, (float*)zmax_dev, (int*)count_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_lidar_to_occupancy(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame, float x0, float y0, float cell, int nx, int ny,
+                           float r_min, float r_max, int no_return_clears, int accumulate, void* hit_dev, void* miss_dev, void* stream) {
+  if (!c) return -1;
+  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to map");
+  if (!lidar_dev || !hit_dev) return fail(c, -1, "null scan / hit buffer");
+  if (((uintptr_t)lidar_dev | (uintptr_t)hit_dev | (uintptr_t)miss_dev) & 3) return fail(c, -1, "scan / hit / miss buffer not aligned to 4 bytes");
+  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  if (nx < 1 || ny < 1 || (long long)nx * ny > SMJ_OCC_MAX_CELLS) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, (int)SMJ_OCC_MAX_CELLS);
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
+  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d: a ray would cross more cells than the line arithmetic takes", (int)SMJ_OCC_MAX_STEPS);
+  if (frame == SMJ_FRAME_CAMERA || frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_WORLD or a body id)", frame);
+  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
+  if (!c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int kind = frame == SMJ_FRAME_WORLD ? SMJ_OCC_WORLD : SMJ_OCC_BODY;
+  smj_launch_occ(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.nlidar, c->render.lidar_site, c->render.site_bodyid,
+                 c->render.site_pos, c->render.site_mat, (const float*)lidar_dev, lidar_ld, kind, kind == SMJ_OCC_BODY ? frame : 0, x0, y0, cell,
+                 nx, ny, r_min, r_max, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -140,6 +140,35 @@ class StatusStretchHeightMap:
 
 
 @dataclass
+class StatusStretchOccupancyGrid:
+    """New, without a reference counterpart: the ray-traced 2-D grid of pull_occupancy_grid() (smj_lidar_to_occupancy).  Cell
+    (iy, ix) covers [origin[0] + ix cell, origin[0] + (ix + 1) cell) x [origin[1] + iy cell, origin[1] + (iy + 1) cell) of the xy
+    plane of `frame`; rows follow y.  Device tensors, simulator-owned, not synchronised to the host.  A cell with neither a hit
+    nor a miss was not seen."""
+    time: Any
+    hit: Any            # [B, ny, nx] int32: rays that ended in the cell on something
+    miss: Any           # [B, ny, nx] int32: rays that passed through the cell (or ended in it on nothing)
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "base" or "world"
+
+    def occupancy(self, min_hits: int = 1):
+        """int8 [B, ny, nx] by the ROS convention (nav_msgs/OccupancyGrid): 100 where hit >= min_hits, else 0 where miss > 0,
+        else -1 (unknown)."""
+        import torch
+
+        out = torch.where(self.miss > 0, 0, -1).to(torch.int8)
+        return torch.where(self.hit >= int(min_hits), torch.tensor(100, dtype=torch.int8, device=out.device), out)
+
+    def log_odds(self, l_hit: float = 0.85, l_miss: float = -0.4):
+        """fp32 [B, ny, nx]: l_hit hit + l_miss miss, the log odds of "occupied" under an inverse sensor model that adds l_hit
+        per ray ending in the cell and l_miss per ray passing through; 0 where the cell was not seen."""
+        import torch
+
+        return float(l_hit) * self.hit.to(torch.float32) + float(l_miss) * self.miss.to(torch.float32)
+
+
+@dataclass
 class StatusStretchContacts:
     """New, without a reference counterpart (like `step` / `reset`): the contact list of every env's last physics step and its
     constraint forces -- what MuJoCo users read from MjData.contact and mj_contactForce after mj_step.  Every field is a device

@@ -23,6 +23,7 @@ EXPORTS = ("smj_create", "smj_destroy", "smj_bind", "smj_dims", "smj_reset", "sm
            "smj_base_controller_tick")
 POINT_EXPORTS = ("smj_depth_to_points",)   # include/smj_pointcloud.h (smj.h includes it): the entries declared there
 HEIGHTMAP_EXPORTS = ("smj_depth_to_heightmap",)   # include/smj_heightmap.h (smj.h includes it)
+OCCUPANCY_EXPORTS = ("smj_lidar_to_occupancy",)   # include/smj_occupancy.h (smj.h includes it)
 FRAME_CAMERA, FRAME_WORLD = -1, -2   # smj_depth_to_points: frame >= 0 is the frame of that fused body
 
 _lib = None
@@ -83,6 +84,7 @@ def load() -> ctypes.CDLL:
     L.smj_depth_to_points.argtypes = [vp, ci, ci, ci, ctypes.c_float, vp, ci, ci, vp, vp]
     cf = ctypes.c_float
     L.smj_depth_to_heightmap.argtypes = [vp, ci, ci, ci, cf, vp, ci, ci, cf, cf, cf, ci, ci, cf, cf, ci, vp, vp, vp]
+    L.smj_lidar_to_occupancy.argtypes = [vp, vp, cl, ci, cf, cf, cf, ci, ci, cf, cf, ci, ci, vp, vp, vp]
     L.smj_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_double]
     L.smj_base_controller_tick.argtypes = [vp, vp]
     L.smj_comm_init.argtypes = [vp, ci, ci, ctypes.c_char_p, ctypes.c_double]

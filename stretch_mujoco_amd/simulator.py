@@ -22,7 +22,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchHeightMap, StatusStretchJoints, StatusStretchSensors
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchHeightMap, StatusStretchJoints, StatusStretchOccupancyGrid, StatusStretchSensors
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -142,6 +142,7 @@ class StretchBatchSimulator:
         self._depth = {}
         self._depth_valid = set()   # depth cameras whose image has been rendered (pull_point_cloud(render=False) needs one)
         self._hmaps = {}            # (frame, (ny, nx)) -> the simulator-owned (height, count) of pull_height_map
+        self._occ = {}              # (frame, (ny, nx)) -> the simulator-owned (hit, miss) of pull_occupancy_grid
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
         self.xpose = torch.zeros(dims[D["NBODY"]] * 12, B, **f)
@@ -448,6 +449,63 @@ class StretchBatchSimulator:
             _lib.check(self._L, self._ctx, rc, "smj_depth_to_heightmap")
         return StatusStretchHeightMap(time=self.nstep.to(torch.float64) * self.timestep, height=bufs[0], count=bufs[1], origin=(x0, y0),
                                       cell=cell, frame=frame)
+
+    @_require_connection
+    def pull_occupancy_grid(self, frame: str = "base", origin=(-3.2, -3.2), cell: float = 0.05, shape=(128, 128),
+                            range_limits=(0.2, 5.0), no_return_clears: bool = True, accumulate: bool = False) -> StatusStretchOccupancyGrid:
+        """Ray-traced 2-D occupancy counts around the robot from the lidar scan of the last step, in one HIP pass
+        (smj_lidar_to_occupancy, include/smj_occupancy.h): per cell the rays that end in it on something (`hit`) and the rays
+        that pass through it (`miss`); a cell with neither was not seen.  New, without a reference counterpart: the reference's
+        examples/laser_scan.py turns the ranges into x/y points and stops there.
+
+        frame: "base" (the simulated base_link body frame) or "world".  Cell (iy, ix) covers origin + [ix, ix + 1) cell in x and
+        origin + [iy, iy + 1) cell in y; shape = (ny, nx), ny nx <= 65536.  range_limits = (r_min, r_max), the bounds laser_scan.py
+        filters by: a range below r_min is the robot itself and is dropped, one in [r_min, r_max] is a return, one above r_max or
+        -1 (nothing hit) is no return -- with no_return_clears such a ray is free over r_max, without it the ray is dropped.
+        r_max / cell <= 8192.  accumulate=True adds to the buffers instead of overwriting them: in the world frame that maps across
+        steps.  Needs StretchSensors.base_lidar in sensors_to_use.
+        The tensors are simulator-owned and overwritten (or added to) by the next call with the same (frame, shape)."""
+        if not self._read_flags & _lib.READ_LIDAR:
+            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+        if frame not in ("world", "base"):
+            raise ValueError('frame must be "world" or "base"')
+        try:
+            ny, nx = (int(v) for v in shape)
+            x0, y0 = (float(v) for v in origin)
+            r_min, r_max = (float(v) for v in range_limits)
+        except (TypeError, ValueError):
+            raise ValueError("shape = (ny, nx), origin = (x0, y0), range_limits = (r_min, r_max)") from None
+        if ny < 1 or nx < 1 or ny * nx > 65536:
+            raise ValueError("shape: ny, nx >= 1 and ny * nx <= 65536")
+        cell = float(cell)
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        if not (np.isfinite(x0) and np.isfinite(y0)):
+            raise ValueError("origin must be finite")
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
+            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
+        if np.float32(r_max) / np.float32(cell) > 8192:
+            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        if frame == "base":
+            i = self.names["body"].index("base_link")
+            fr = int(self.model["link_fused"][i])
+            if np.any(np.asarray(self.model["link_relpos"][i], np.float64) != 0) or not torch.equal(
+                    self._quat_mat(self.model["link_relquat"][i], self.device), torch.eye(3, device=self.device)):
+                raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned grid cannot be '
+                                 'corrected afterwards (use frame="world")')
+        else:
+            fr = _lib.FRAME_WORLD
+        key = (frame, (ny, nx))
+        bufs = self._occ.get(key)
+        if bufs is None:
+            bufs = self._occ[key] = (torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device),
+                                     torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device))
+        rc = self._L.smj_lidar_to_occupancy(self._ctx, ctypes.c_void_p(self.lidar.data_ptr()), self.num_envs, fr, x0, y0, cell, nx, ny,
+                                            r_min, r_max, int(bool(no_return_clears)), int(bool(accumulate)),
+                                            ctypes.c_void_p(bufs[0].data_ptr()), ctypes.c_void_p(bufs[1].data_ptr()), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_lidar_to_occupancy")
+        return StatusStretchOccupancyGrid(time=self.nstep.to(torch.float64) * self.timestep, hit=bufs[0], miss=bufs[1], origin=(x0, y0),
+                                          cell=cell, frame=frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

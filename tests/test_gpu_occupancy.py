@@ -1,0 +1,465 @@
+"""2-D occupancy grids from the lidar scan on the HIP path: smj_lidar_to_occupancy through the C-ABI and
+StretchBatchSimulator.pull_occupancy_grid.
+
+One simulator for the module, the rig of tests/test_gpu_height_map.py: stretch_scene, three envs driven apart, 200 steps, the lidar
+on.  The kernel is compared with the fp64 reference (tests/occupancy_ref.py) fed the kernel's own inputs -- the same fp32 scan, the
+XPOSE array, the blob's site tables, and the fp32 values of origin and cell -- by that file's comparison rule: every cell of both
+layers, n_lo <= count <= n_hi, with at most 2 % (7) ambiguous rays per env and case, printed.  All rays of an env share one origin,
+so the grid's origin is searched on a 2^-10 lattice until the reference keeps every laser off the cell edges and within the cap
+(pytest.fail if no candidate does).  Everything else is exact: integer equalities.
+
+The band test shifts y0 by 48 cells of 0.0625 m; y - y0 then rounds differently in the two calls, so a point within 2^-22 m of a
+row edge could change rows.  Its origin is taken so that the REFERENCE has no ray end that close, margin included; then the
+equality is bit for bit over all cells."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import occupancy_ref as ref
+from point_cloud_ref import body_pose
+
+pytestmark = pytest.mark.gpu
+
+B = 3
+K = 360
+NaN = float("nan")
+INF = float("inf")
+LIMITS = (0.2, 9.5)
+
+
+def f32(v):
+    return float(np.float32(v))
+
+
+class Rig:
+    pass
+
+
+@pytest.fixture(scope="module")
+def rig():
+    from stretch_mujoco_amd import StretchBatchSimulator, lib
+    from stretch_mujoco_amd.enums import StretchSensors
+
+    sim = StretchBatchSimulator(num_envs=B, device="cuda:0", sensors_to_use=[StretchSensors.base_lidar], solver="newton", scene="stretch_scene")
+    sim.start(home=False)
+    jn = {n: i for i, n in enumerate(sim.names["joint"])}
+    an = {n: i for i, n in enumerate(sim.names["actuator"])}
+    adr = sim.model["jnt_qposadr"]
+    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
+    ctrl = np.zeros((sim.nu, B))
+    for e, (x, y, yaw, lift) in enumerate([(0.0, 0.0, 0.0, 0.6), (-0.3, 0.2, 0.5, 0.3), (-0.5, -0.3, -0.7, 0.45)]):      # per env: base x, y, yaw; lift
+        q[0:2, e] = [x, y]
+        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
+        q[adr[jn["joint_lift"]], e] = lift
+        ctrl[an["lift"], e] = lift
+    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
+    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
+    sim.step(200)
+    torch.cuda.synchronize()
+    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
+    r = Rig()
+    r.sim, r.L, r.lib = sim, lib.load(), lib
+    assert sim.nlidar == K
+    r.scan = sim.lidar[:K].clone()                      # [K, B] batch-major, ld = B: what SMJ_SLOT_LIDAR holds
+    r.scan_host = r.scan.cpu().numpy()
+    r.xpose = sim.xpose.cpu().numpy().astype(np.float64)
+    to32 = lambda v: np.asarray(v, np.float64).astype(np.float32).astype(np.float64)      # the library rounds the tables to fp32
+    sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
+    r.site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
+    r.site_pos = to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
+    r.lz = to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
+    r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
+    r.cache = {}
+    yield r
+    sim.stop()
+
+
+def _geometry(r, frame, xpose=None):
+    """Per env (o, d, So, Sd) of tests/occupancy_ref.py from the XPOSE array and the site tables."""
+    key = ("geom", frame)
+    if xpose is None and key in r.cache:
+        return r.cache[key]
+    xp = r.xpose if xpose is None else xpose
+    poses = {b: body_pose(xp, int(b)) for b in set(r.site_body.tolist()) | {r.base}}
+    out = []
+    for e in range(xp.shape[1]):
+        bp = np.stack([poses[int(b)][0][e] for b in r.site_body])
+        bm = np.stack([poses[int(b)][1][e] for b in r.site_body])
+        fp, fm = (poses[r.base][0][e], poses[r.base][1][e]) if frame == "base" else (None, None)
+        out.append(ref.ray_geometry(bp, bm, r.site_pos, r.lz, fp, fm))
+    if xpose is None:
+        r.cache[key] = out
+    return out
+
+
+def _fid(r, frame):
+    return {"world": r.lib.FRAME_WORLD, "base": r.base}[frame]
+
+
+def _new(r, nx, ny, fill=7):
+    return (torch.full((B, ny, nx), fill, dtype=torch.int32, device=r.sim.device), torch.full((B, ny, nx), fill, dtype=torch.int32, device=r.sim.device))
+
+
+def _occ(r, scan, frame, x0, y0, cell, nx, ny, r_min, r_max, clears=1, acc=0, out=None, miss=True, ctx=None, rc=0, ld=None):
+    if out is None:
+        out = _new(r, nx, ny)
+    got = r.L.smj_lidar_to_occupancy(ctx or r.sim._ctx, ctypes.c_void_p(scan.data_ptr()), scan.stride(0) if ld is None else ld, frame, x0, y0, cell, nx, ny,
+                                     r_min, r_max, clears, acc, ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()) if miss else None,
+                                     r.sim._stream())
+    assert got == rc, (got, r.L.smj_last_error(ctx or r.sim._ctx))
+    return out
+
+
+def _lattice(cx, cy, nx, ny, cell):
+    """Candidate origins of a grid centred near (cx, cy), on a 2^-10 lattice."""
+    bx, by = np.round((cx - nx * cell / 2) * 1024) / 1024, np.round((cy - ny * cell / 2) * 1024) / 1024
+    return [(bx - j / 1024, by - ((5 * j) % 64) / 1024) for j in range(64)]
+
+
+def _origin(r, frame, scan_host, nx, ny, cell, r_min, r_max, clears):
+    geoms = _geometry(r, frame)
+    cx, cy = geoms[0][0][0]      # env 0's laser: inside every grid, the small one too
+    got = ref.choose_origin(_lattice(cx, cy, nx, ny, cell), [(*g, scan_host[:, e]) for e, g in enumerate(geoms)], f32(cell), nx, ny, f32(r_min), f32(r_max), clears)
+    if got is None:
+        pytest.fail("no candidate origin keeps the lasers off the cell edges and the ambiguous rays within 2 %")
+    return got
+
+
+def _compare(tag, hit, miss, bds):
+    torch.cuda.synchronize()
+    h, m = hit.cpu().numpy(), miss.cpu().numpy()
+    for e, bd in enumerate(bds):
+        share = ref.ambiguous_share(bd)
+        print(tag, "env", e, "returns", bd.returns, "clears", bd.clears, "dropped", bd.dropped, "sure", bd.sure, "ambiguous", bd.ambiguous,
+              "share %.3f %%" % (100 * share), "hit cells", int((h[e] > 0).sum()), "missed cells", int((m[e] > 0).sum()))
+        assert share <= ref.MAX_AMBIGUOUS, (tag, e, share)
+        bad = ref.check_grid(h[e], m[e], bd)
+        assert not bad, (tag, e, len(bad), bad[:5])
+    return h, m
+
+
+def test_scan_of_the_rig_returns(rig):
+    for e in range(B):
+        s = rig.scan_host[:, e]
+        n = int(((s >= f32(LIMITS[0])) & (s <= f32(LIMITS[1]))).sum())
+        print("env", e, "rays returning within", LIMITS, ":", n, "on the robot itself:", int(((s >= 0) & (s < f32(LIMITS[0]))).sum()), "no hit:", int((s < 0).sum()))
+        assert n >= 50, (e, n)
+
+
+@pytest.mark.parametrize("frame", ["world", "base"])
+def test_kernel_against_the_reference_on_its_own_inputs(rig, frame):
+    r = rig
+    seen = 0
+    for r_max in (9.5, 2.0):
+        for clears in (0, 1):
+            for nx, ny in ((16, 12), (64, 64), (61, 83), (64, 96)):
+                (x0, y0), bds = _origin(r, frame, r.scan_host, nx, ny, 0.05, 0.2, r_max, clears)
+                hit, miss = _occ(r, r.scan, _fid(r, frame), x0, y0, f32(0.05), nx, ny, f32(0.2), f32(r_max), clears)
+                h, m = _compare(f"{frame} r_max {r_max} clears {clears} grid {nx}x{ny} origin ({x0}, {y0})", hit, miss, bds)
+                seen += int((m > 0).sum())
+                assert int((m > 0).sum()) > nx and (int((h > 0).sum()) > 0 or nx < 61 or r_max < 9.5)      # not about empty grids
+    assert seen > 10000
+
+
+def _bare_context(r, n):
+    """A context with XPOSE alone bound, to identity rotations and zero translations: ray k is (site_pos, +Z column) as stored."""
+    sim = r.sim
+    ctx = ctypes.c_void_p()
+    assert r.L.smj_create(sim._blob, len(sim._blob), n, 0, ctypes.byref(ctx)) == 0
+    xp = torch.zeros(sim.xpose.shape[0], n, dtype=torch.float32, device=sim.device)
+    for k in (3, 7, 11):
+        xp[k::12] = 1.0
+    assert r.L.smj_bind(ctx, r.lib.SLOT["XPOSE"], ctypes.c_void_p(xp.data_ptr()), n) == 0
+    return ctx, xp
+
+
+def test_exact_case_unit_ranges_from_identity_poses(rig):
+    """Identity poses, world frame, cell 0.0625 (inv_cell = 16 exactly), every range 1.0: o = site_pos and d = the site's +Z column
+    exactly, and o + r d is one rounding with or without FMA.  Replicated in np.float32 with the origin on a 2^-10 lattice that keeps
+    every end point and the laser more than 2e-5 cells from an edge; both layers are then equal as integers."""
+    r = rig
+    ctx, xp = _bare_context(r, B)
+    try:
+        o32, d32 = r.site_pos[:, :2].astype(np.float32), r.lz[:, :2].astype(np.float32)
+        e32 = o32 + np.float32(1.0) * d32
+        nx, ny = 64, 72      # 4 m x 4.5 m around the laser: two bands, every ray ends inside
+        cell = np.float32(0.0625)
+        for j in range(64):
+            x0, y0 = np.float32(np.round(float(o32[0, 0])) - 2.0 - j / 1024), np.float32(np.round(float(o32[0, 1])) - 2.25 - ((5 * j) % 64) / 1024)
+            fo = (o32 - np.array([x0, y0], np.float32)) * np.float32(16)
+            fe = (e32 - np.array([x0, y0], np.float32)) * np.float32(16)
+            if min(np.abs(fo - np.round(fo)).min(), np.abs(fe - np.round(fe)).min()) > 2e-5:
+                break
+        else:
+            pytest.fail("no origin keeps the laser and the end points off the cell edges")
+        a, b = np.floor(fo).astype(np.int64), np.floor(fe).astype(np.int64)
+        want_hit, want_miss, want_clear = (np.zeros((ny, nx), np.int64) for _ in range(3))
+        for k in range(K):
+            xs, ys = ref.line_cells(int(a[k, 0]), int(a[k, 1]), int(b[k, 0]), int(b[k, 1]))
+            ok = (xs >= 0) & (xs < nx) & (ys >= 0) & (ys < ny)
+            np.add.at(want_clear, (ys[ok], xs[ok]), 1)
+            ok[-1] = False
+            np.add.at(want_miss, (ys[ok], xs[ok]), 1)
+            if 0 <= b[k, 0] < nx and 0 <= b[k, 1] < ny:
+                want_hit[b[k, 1], b[k, 0]] += 1
+        assert want_hit.sum() == K and want_miss.sum() > 10 * K and (want_hit + want_miss == 0).any()
+        ld = B + 2
+        scan = torch.full((K, ld), 3.25, dtype=torch.float32, device=r.sim.device)      # the two sentinel columns would draw other rays
+        grid = (float(x0), float(y0), float(cell), nx, ny)
+        scan[:, :B] = 1.0
+        hit, miss = _occ(r, scan, r.lib.FRAME_WORLD, *grid, f32(0.2), 2.0, 1, ctx=ctx, ld=ld)
+        scan[:, :B] = -1.0
+        chit, cmiss = _occ(r, scan, r.lib.FRAME_WORLD, *grid, f32(0.2), 1.0, 1, ctx=ctx, ld=ld)      # nothing hit: free over r_max = 1
+        dhit, dmiss = _occ(r, scan, r.lib.FRAME_WORLD, *grid, f32(0.2), 1.0, 0, ctx=ctx, ld=ld)      # ... or dropped
+        scan[:, :B] = 0.1
+        shit, smiss = _occ(r, scan, r.lib.FRAME_WORLD, *grid, f32(0.2), 2.0, 1, ctx=ctx, ld=ld)      # the robot itself
+        torch.cuda.synchronize()
+        print("exact case: origin", float(x0), float(y0), "hit cells", int((want_hit > 0).sum()), "missed cells", int((want_miss > 0).sum()))
+        assert (scan[:, B:] == 3.25).all()
+        for e in range(B):
+            assert np.array_equal(hit[e].cpu().numpy(), want_hit), (e, np.argwhere(hit[e].cpu().numpy() != want_hit)[:5])
+            assert np.array_equal(miss[e].cpu().numpy(), want_miss), (e, np.argwhere(miss[e].cpu().numpy() != want_miss)[:5])
+            assert int(chit[e].abs().sum()) == 0 and np.array_equal(cmiss[e].cpu().numpy(), want_clear)
+        for t in (dhit, dmiss, shit, smiss):
+            assert int(t.abs().sum()) == 0
+    finally:
+        r.L.smj_destroy(ctx)
+
+
+def _second_scan(r):
+    """Another scan of the same robots: the rays rolled by 17 and shortened, a few without a return."""
+    s = torch.roll(r.scan, 17, 0) * 0.8
+    s[::23] = -1.0
+    return s.contiguous()
+
+
+def test_invariants(rig):
+    r = rig
+    other = _second_scan(r)
+    for frame in ("world", "base"):
+        for nx, ny in ((64, 64), (61, 83)):
+            grid = (f32(-1.613), f32(-1.587 if ny == 64 else -2.087), f32(0.05), nx, ny, f32(0.2), f32(5.0))
+
+            def call(scan, **kw):
+                return _occ(r, scan, _fid(r, frame), *grid, **kw)
+
+            a, a2, b = call(r.scan), call(r.scan), call(other)
+            assert torch.equal(a[0], a2[0]) and torch.equal(a[1], a2[1])      # two calls, identical arrays
+            ab = call(other, acc=1, out=call(r.scan))
+            ba = call(r.scan, acc=1, out=call(other))
+            torch.cuda.synchronize()
+            assert torch.equal(ab[0], a[0] + b[0]) and torch.equal(ab[1], a[1] + b[1])
+            assert torch.equal(ab[0], ba[0]) and torch.equal(ab[1], ba[1])
+            for t in (a, b):
+                assert int((t[0] + t[1]).max()) <= K and int(t[0].min()) >= 0 and int(t[1].min()) >= 0
+            assert int((a[0] > 0).sum()) > 20 and int((a[1] > 0).sum()) > 500 and not torch.equal(a[0], b[0])
+            # without a miss buffer the hits are the same and nothing else is touched; accumulating without one adds the hits
+            h_only = _new(r, nx, ny)
+            call(r.scan, out=h_only, miss=False)
+            assert torch.equal(h_only[0], a[0]) and int((h_only[1] != 7).sum()) == 0
+            call(other, out=h_only, miss=False, acc=1)
+            assert torch.equal(h_only[0], ab[0]) and int((h_only[1] != 7).sum()) == 0
+            # what a ray without a return does changes the miss layer alone
+            n0 = call(r.scan, clears=0)
+            assert torch.equal(n0[0], a[0]) and bool((n0[1] <= a[1]).all())
+            short = _occ(r, r.scan, _fid(r, frame), *grid[:5], f32(0.2), f32(1.0), clears=1), _occ(r, r.scan, _fid(r, frame), *grid[:5], f32(0.2), f32(1.0), clears=0)
+            assert torch.equal(short[0][0], short[1][0]) and int((short[0][1] - short[1][1]).sum()) > 0
+
+
+def test_bands_equal_the_two_half_grids(rig):
+    """64 x 96 cells at 0.0625 m are two bands.  The grid equals, bit for bit, its two halves of 48 rows computed by two calls with
+    y0 and y0 + 3 (module docstring: y0 is taken so that the reference has no ray end within its margin + 2^-22 m of a row edge)."""
+    r = rig
+    nx, ny, cell = 64, 96, 0.0625
+    geoms = _geometry(r, "base")
+    for j in range(16):
+        x0, y0 = -2.0 - ((3 * j) % 16) / 256, -3.0 - j / 256
+        ok = True
+        for e, (o, d, So, Sd) in enumerate(geoms):
+            ok &= ref.origin_margin_cells(o, So, x0, y0, cell) > 0      # the laser itself off every edge, as in every other comparison
+            kind, length = ref.classify(r.scan_host[:, e], f32(LIMITS[0]), f32(LIMITS[1]), 1)
+            keep = kind != ref.DROP
+            for p, S in ((o[keep], So[keep]), ((o + length[:, None] * d)[keep], (So + np.abs(length)[:, None] * Sd)[keep])):
+                m = ref.EPS * S[:, 1] + 2.0 ** -22 * (np.abs(p[:, 0] - x0) + np.abs(p[:, 1] + 3.0) + 1 / 16) + 2.0 ** -22
+                ok &= bool((np.floor((p[:, 1] - m - y0) / cell) == np.floor((p[:, 1] + m - y0) / cell)).all())
+        if ok:
+            break
+    else:
+        pytest.fail("every candidate origin has a ray end within rounding of a row edge")
+    args = (r.scan, r.base, x0)
+    lim = (f32(LIMITS[0]), f32(LIMITS[1]))
+    full = _occ(r, *args, y0, cell, nx, ny, *lim)
+    lo = _occ(r, *args, y0, cell, nx, 48, *lim)
+    hi = _occ(r, *args, y0 + 48 * cell, cell, nx, 48, *lim)
+    torch.cuda.synchronize()
+    print("bands: y0", y0, "seen cells", int(((full[0] + full[1]) > 0).sum()), int(((lo[0] + lo[1]) > 0).sum()), int(((hi[0] + hi[1]) > 0).sum()))
+    for k in (0, 1):
+        assert torch.equal(full[k][:, :48].contiguous(), lo[k]) and torch.equal(full[k][:, 48:].contiguous(), hi[k])
+        assert int((lo[k] > 0).sum()) > 0 and int((hi[k] > 0).sum()) > 0
+    bds = [ref.bounds(*g, r.scan_host[:, e], x0, y0, cell, nx, ny, *lim, 1) for e, g in enumerate(geoms)]
+    _compare("bands 64x96", *full, bds)
+
+
+def test_nothing_outside_the_outputs_is_written_and_alignment_does_not_matter(rig):
+    """Grids of one and two bands.  The outputs as views 4 bytes past a 16-byte boundary inside buffers of sentinels: the guards stay
+    untouched and the values are those of the aligned call; the same with the scan 4 bytes past a 16-byte boundary, with both,
+    and with only one of the two outputs misaligned."""
+    r = rig
+    dev = r.sim.device
+    assert r.scan.data_ptr() % 16 == 0
+    sbig = torch.full((1 + K * B + 3,), -77.0, dtype=torch.float32, device=dev)
+    sview = sbig[1: 1 + K * B].view(K, B)
+    sview.copy_(r.scan)
+    assert sview.data_ptr() % 16 == 4
+    for frame in ("base", "world"):
+        for nx, ny in ((16, 12), (64, 64), (61, 83)):
+            grid = (f32(-nx * 0.05 / 2 + 0.013), f32(-ny * 0.05 / 2 - 0.013), f32(0.05), nx, ny, f32(0.2), f32(9.5))
+            want = _occ(r, r.scan, _fid(r, frame), *grid)
+            assert want[0].data_ptr() % 16 == 0 and want[1].data_ptr() % 16 == 0
+            cells, pad = B * nx * ny, 37      # 37 words = 148 bytes = 4 mod 16
+            results = []
+            for scan, hpad, mpad in ((r.scan, pad, pad), (sview, pad, pad), (r.scan, pad, 36), (r.scan, 36, pad), (sview, 36, 36)):
+                hbig = torch.full((hpad + cells + pad,), -12345, dtype=torch.int32, device=dev)
+                mbig = torch.full((mpad + cells + pad,), -12345, dtype=torch.int32, device=dev)
+                hv, mv = hbig[hpad: hpad + cells].view(B, ny, nx), mbig[mpad: mpad + cells].view(B, ny, nx)
+                assert hv.data_ptr() % 16 == (4 * hpad) % 16 and mv.data_ptr() % 16 == (4 * mpad) % 16
+                _occ(r, scan, _fid(r, frame), *grid, out=(hv, mv))
+                results.append((hbig, mbig, hpad, mpad))
+            torch.cuda.synchronize()
+            assert int((want[1] > 0).sum()) > 0 and (int((want[0] > 0).sum()) > 0 or nx < 61)      # (nothing stands within 0.4 m of the robot)
+            for hbig, mbig, hpad, mpad in results:
+                for big, p, w in ((hbig, hpad, want[0]), (mbig, mpad, want[1])):
+                    assert (big[:p] == -12345).all() and (big[p + cells:] == -12345).all()
+                    assert torch.equal(big[p: p + cells].view(B, ny, nx), w)
+    assert sbig[0] == -77.0 and (sbig[1 + K * B:] == -77.0).all() and torch.equal(sview, r.scan)
+
+
+def test_error_codes_and_a_refused_call_writes_nothing(rig):
+    r = rig
+    L, sim = r.L, r.sim
+    nx = ny = 64
+    out = (torch.zeros(B, ny, nx, dtype=torch.int32, device=sim.device), torch.zeros(B, ny, nx, dtype=torch.int32, device=sim.device))
+    good = dict(ld=B, frame=r.lib.FRAME_WORLD, x0=-1.6, y0=-1.6, cell=0.05, nx=nx, ny=ny, r_min=0.2, r_max=5.0)
+    bad = [dict(ld=B - 1), dict(ld=0), dict(nx=0), dict(ny=0), dict(nx=-4), dict(nx=257, ny=256), dict(nx=65537, ny=1), dict(cell=0.0), dict(cell=-0.05),
+           dict(cell=INF), dict(cell=NaN), dict(x0=INF), dict(x0=NaN), dict(y0=-INF), dict(y0=NaN), dict(r_min=NaN), dict(r_max=NaN), dict(r_max=INF),
+           dict(r_min=-0.1), dict(r_min=-INF), dict(r_min=5.5), dict(r_max=0.1), dict(cell=0.0005, r_max=4.2), dict(cell=1e-3, r_max=8.5),
+           dict(frame=r.lib.FRAME_CAMERA), dict(frame=-3), dict(frame=10 ** 6), dict(frame=sim.xpose.shape[0] // 12)]
+    sp, hp, mp = r.scan.data_ptr(), out[0].data_ptr(), out[1].data_ptr()
+
+    def call(a, s=sp, h=hp, m=mp, ctx=None):
+        return L.smj_lidar_to_occupancy(ctx or sim._ctx, ctypes.c_void_p(s) if s else None, a["ld"], a["frame"], a["x0"], a["y0"], a["cell"], a["nx"], a["ny"],
+                                        a["r_min"], a["r_max"], 1, 0, ctypes.c_void_p(h) if h else None, ctypes.c_void_p(m) if m else None, sim._stream())
+
+    for change in bad:
+        rc = call(dict(good, **change))
+        assert rc == -1, (change, rc)
+        assert L.smj_last_error(sim._ctx)
+    for s, h, m in ((None, hp, mp), (sp, None, mp), (sp + 2, hp, mp), (sp, hp + 1, mp), (sp, hp, mp + 2)):      # null / misaligned pointers
+        assert call(good, s, h, m) == -1, (s, h, m)
+    torch.cuda.synchronize()
+    assert int(out[0].abs().max()) == 0 and int(out[1].abs().max()) == 0        # a refused call writes nothing
+    # accepted: the largest grid, the longest ray (r_max / cell = 8192), a null miss buffer, the last body as the frame
+    _occ(r, r.scan, r.lib.FRAME_WORLD, -6.4, -6.4, 0.05, 256, 256, 0.2, 5.0)
+    _occ(r, r.scan, r.lib.FRAME_WORLD, -1.6, -1.6, 0.0009765625, 64, 64, 0.2, 8.0)
+    _occ(r, r.scan, sim.xpose.shape[0] // 12 - 1, -1.6, -1.6, 0.05, 64, 64, 0.0, 0.0, miss=False)
+    torch.cuda.synchronize()
+    # a bare context (nothing bound): every frame needs XPOSE (-5)
+    from stretch_mujoco_amd import model_blob
+
+    bare = ctypes.c_void_p()
+    assert L.smj_create(sim._blob, len(sim._blob), B, 0, ctypes.byref(bare)) == 0
+    try:
+        for frame in (r.lib.FRAME_WORLD, 0, r.base):
+            assert call(dict(good, frame=frame), ctx=bare) == -5
+            assert b"XPOSE" in L.smj_last_error(bare)
+        assert call(dict(good, nx=0), ctx=bare) == -1
+    finally:
+        L.smj_destroy(bare)
+    # models without a lidar: no ray-casting tables at all, and tables with no rangefinder
+    no_tables = {k: v for k, v in sim.model.items() if k != "sensor_lidar_static"}
+    no_rays = dict(sim.model, sensor_lidar_site=np.zeros(0, np.int32), sensor_lidar_static=np.zeros(0, np.float64))
+    for model in (no_tables, no_rays):
+        blob = model_blob.dumps(model)
+        ctx = ctypes.c_void_p()
+        assert L.smj_create(blob, len(blob), B, 0, ctypes.byref(ctx)) == 0, L.smj_last_error(ctx)
+        try:
+            assert call(good, ctx=ctx) == -6
+            assert b"lidar" in L.smj_last_error(ctx)
+        finally:
+            L.smj_destroy(ctx)
+    torch.cuda.synchronize()
+    assert int(out[0].abs().max()) == 0 and int(out[1].abs().max()) == 0
+
+
+def test_python_api(rig):
+    r = rig
+    sim = r.sim
+    from stretch_mujoco_amd import StretchBatchSimulator
+    from stretch_mujoco_amd.datamodels import StatusStretchOccupancyGrid
+    from stretch_mujoco_amd.lib import SmjError
+
+    og = sim.pull_occupancy_grid()
+    assert isinstance(og, StatusStretchOccupancyGrid) and og.frame == "base" and og.cell == 0.05 and og.origin == (-3.2, -3.2)
+    assert tuple(og.hit.shape) == tuple(og.miss.shape) == (B, 128, 128) and og.hit.dtype == og.miss.dtype == torch.int32
+    assert tuple(og.time.shape) == (B,)
+    again = sim.pull_occupancy_grid()
+    assert again.hit.data_ptr() == og.hit.data_ptr() and again.miss.data_ptr() == og.miss.data_ptr()      # simulator-owned, keyed by (frame, shape)
+    assert sim.pull_occupancy_grid(frame="world").hit.data_ptr() != og.hit.data_ptr()
+    assert sim.pull_occupancy_grid(shape=(48, 64)).hit.data_ptr() != og.hit.data_ptr() and tuple(sim.pull_occupancy_grid(shape=(48, 64)).hit.shape) == (B, 48, 64)
+    # == the C call on the scan of the last step, bit for bit
+    for frame, kw in (("base", dict()), ("world", dict(origin=(-3.7, -3.1), range_limits=(0.2, 9.5), no_return_clears=False))):
+        got = sim.pull_occupancy_grid(frame=frame, **kw)
+        x0, y0 = kw.get("origin", (-3.2, -3.2))
+        lim = kw.get("range_limits", (0.2, 5.0))
+        want = _occ(r, sim.lidar, _fid(r, frame), x0, y0, 0.05, 128, 128, *lim, clears=int(kw.get("no_return_clears", True)))
+        torch.cuda.synchronize()
+        assert torch.equal(got.hit, want[0]) and torch.equal(got.miss, want[1]) and int((got.hit > 0).sum((1, 2)).min()) > 0
+    # the helpers
+    og = sim.pull_occupancy_grid()
+    occ, lo = og.occupancy(), og.log_odds()
+    assert occ.dtype == torch.int8 and lo.dtype == torch.float32 and tuple(occ.shape) == tuple(lo.shape) == (B, 128, 128)
+    assert set(torch.unique(occ).tolist()) == {-1, 0, 100}
+    assert torch.equal(occ == 100, og.hit >= 1) and torch.equal(occ == 0, (og.hit < 1) & (og.miss > 0)) and torch.equal(occ == -1, (og.hit + og.miss) == 0)
+    occ3 = og.occupancy(min_hits=3)
+    assert torch.equal(occ3 == 100, og.hit >= 3) and torch.equal(occ3 == 0, (og.hit < 3) & (og.miss > 0)) and int((occ3 == 100).sum()) < int((occ == 100).sum())
+    only_hit, only_miss = (og.hit > 0) & (og.miss == 0), (og.hit == 0) & (og.miss > 0)
+    assert int(only_hit.sum()) > 0 and int(only_miss.sum()) > 0
+    assert bool((lo[only_hit] > 0).all()) and bool((lo[only_miss] < 0).all()) and bool((lo[(og.hit + og.miss) == 0] == 0).all())
+    assert torch.equal(og.log_odds(1.0, -1.0), (og.hit - og.miss).to(torch.float32))
+    # accumulate over two steps in the world frame == the sum of the two single maps
+    kw = dict(frame="world", origin=(-3.7, -3.1), shape=(96, 64))
+    first = sim.pull_occupancy_grid(**kw)
+    h1, m1 = first.hit.clone(), first.miss.clone()
+    sim.ctrl[0], sim.ctrl[1] = 2.0, -1.0      # the wheels: the base turns and moves
+    sim.step(40)
+    acc = sim.pull_occupancy_grid(accumulate=True, **kw)
+    ha, ma = acc.hit.clone(), acc.miss.clone()
+    second = sim.pull_occupancy_grid(**kw)
+    torch.cuda.synchronize()
+    assert torch.equal(ha, h1 + second.hit) and torch.equal(ma, m1 + second.miss) and not torch.equal(second.hit, h1)
+    # validation
+    for bad in (dict(frame="odom"), dict(frame="camera"), dict(shape=(0, 4)), dict(shape=(257, 256)), dict(shape=(4,)), dict(cell=0.0), dict(cell=NaN),
+                dict(origin=(INF, 0.0)), dict(origin=(0.0,)), dict(range_limits=(1.0, 0.5)), dict(range_limits=(NaN, 1.0)), dict(range_limits=(-0.1, 1.0)),
+                dict(range_limits=(0.2, INF)), dict(range_limits=(0.2,)), dict(cell=0.001, range_limits=(0.2, 8.5))):
+        with pytest.raises(ValueError):
+            sim.pull_occupancy_grid(**bad)
+    # base_link at a fixed pose inside its fused body (no shipped model: the entry is changed for the length of this check)
+    i = sim.names["body"].index("base_link")
+    keep = sim.model["link_relpos"][i].copy()
+    try:
+        sim.model["link_relpos"][i] = [0.3, -0.2, 0.1]
+        with pytest.raises(ValueError, match="base_link"):
+            sim.pull_occupancy_grid()
+        sim.pull_occupancy_grid(frame="world")
+    finally:
+        sim.model["link_relpos"][i] = keep
+    # without the lidar sensor there is no scan
+    blind = StretchBatchSimulator(num_envs=1, device="cuda:0", solver="newton", scene="stretch_scene")
+    blind.start(home=False)
+    try:
+        with pytest.raises(SmjError, match="base_lidar"):
+            blind.pull_occupancy_grid()
+    finally:
+        blind.stop()

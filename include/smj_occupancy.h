@@ -49,4 +49,5 @@ int smj_lidar_to_occupancy(smj_ctx* ctx, const void* lidar_dev, long lidar_ld, i
 #ifdef __cplusplus
 }
 #endif
+#include "smj_distance.h"
 #endif

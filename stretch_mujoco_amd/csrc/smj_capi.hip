@@ -23,6 +23,7 @@
 #include "smj_points.h"
 #include "smj_hmap.h"
 #include "smj_occ.h"
+#include "smj_edt.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -741,6 +742,34 @@ int smj_lidar_to_occupancy(smj_ctx* c, const void* lidar_dev, long lidar_ld, int
   smj_launch_occ(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.nlidar, c->render.lidar_site, c->render.site_bodyid,
                  c->render.site_pos, c->render.site_mat, (const float*)lidar_dev, lidar_ld, kind, kind == SMJ_OCC_BODY ? frame : 0, x0, y0, cell,
                  nx, ny, r_min, r_max, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_occupancy_to_distance(smj_ctx* c, const void* hit_dev, const void* miss_dev, int nx, int ny, int min_hits, int unknown_is_obstacle,
+                              int max_dist_cells, void* dist2_dev, void* nearest_dev, void* stream) {
+  if (!c) return -1;
+  if (!hit_dev || !dist2_dev) return fail(c, -1, "null hit / dist2 buffer");
+  if (((uintptr_t)hit_dev | (uintptr_t)miss_dev | (uintptr_t)dist2_dev | (uintptr_t)nearest_dev) & 3) return fail(c, -1, "hit / miss / dist2 / nearest buffer not aligned to 4 bytes");
+  if (nx < 1 || ny < 1 || nx > SMJ_EDT_MAX_SIDE || ny > SMJ_EDT_MAX_SIDE || (long long)nx * ny > SMJ_EDT_MAX_CELLS)
+    return fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, (int)SMJ_EDT_MAX_SIDE, (int)SMJ_EDT_MAX_CELLS);
+  if (min_hits < 1) return fail(c, -1, "min_hits %d below 1: every cell would be an obstacle", min_hits);
+  if (max_dist_cells < 0) return fail(c, -1, "max_dist_cells %d is negative (0 = no bound)", max_dist_cells);
+  if (unknown_is_obstacle && !miss_dev) return fail(c, -1, "unknown_is_obstacle needs the miss layer");
+  // several workgroups of an env read the grid while others store: no output may share a byte with an input or the other output
+  const uintptr_t bytes = (uintptr_t)c->num_envs * (uintptr_t)nx * (uintptr_t)ny * 4u;
+  const uintptr_t in[2] = {(uintptr_t)hit_dev, (uintptr_t)miss_dev}, out[2] = {(uintptr_t)dist2_dev, (uintptr_t)nearest_dev};
+  for (int o = 0; o < 2; o++) {
+    if (!out[o]) continue;
+    for (int i = 0; i < 2; i++)
+      if (in[i] && out[o] < in[i] + bytes && in[i] < out[o] + bytes) return fail(c, -1, "an output range overlaps an input range");
+  }
+  if (out[1] && out[0] < out[1] + bytes && out[1] < out[0] + bytes) return fail(c, -1, "the dist2 and nearest ranges overlap");
+  HIPCHK(c, hipSetDevice(c->device));
+  // no cell pair is further apart than sqrt(2) 4095 cells: a larger bound is no bound (and R * R stays an int)
+  const int R = max_dist_cells >= 2 * SMJ_EDT_MAX_SIDE ? 0 : max_dist_cells;
+  smj_launch_edt(c->num_envs, (const int*)hit_dev, (const int*)miss_dev, nx, ny, min_hits, unknown_is_obstacle != 0, R, (int*)dist2_dev,
+                 (int*)nearest_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

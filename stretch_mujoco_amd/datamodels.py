@@ -169,6 +169,60 @@ class StatusStretchOccupancyGrid:
 
 
 @dataclass
+class StatusStretchDistanceField:
+    """New, without a reference counterpart: the exact distance field of pull_distance_field() (smj_occupancy_to_distance) over a
+    grid laid out as StatusStretchOccupancyGrid's.  `dist2` and `nearest` are exact integers in cells; the helpers turn them into
+    metres and costs in torch.  Device tensors, simulator-owned, not synchronised to the host."""
+    time: Any
+    dist2: Any          # [B, ny, nx] int32: squared distance in cells to the nearest obstacle cell, 0 on one, NONE where there is none in reach
+    nearest: Any        # [B, ny, nx] int32 or None: linear index iy nx + ix of that obstacle (the smallest among equally near ones), -1 where none
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "base" or "world" ("grid" for a bare mask)
+
+    NONE = 1 << 30      # SMJ_DIST_NONE
+
+    def distance(self):
+        """fp32 [B, ny, nx]: sqrt(dist2) cell in metres, inf where there is no obstacle in reach."""
+        import torch
+
+        d = torch.sqrt(self.dist2.to(torch.float32)) * float(self.cell)
+        return torch.where(self.dist2 >= self.NONE, torch.tensor(float("inf"), dtype=torch.float32, device=d.device), d)
+
+    def nearest_offset(self):
+        """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell to its nearest obstacle, zeros where there is none.  Needs
+        pull_distance_field(nearest=True)."""
+        import torch
+
+        if self.nearest is None:
+            raise ValueError("nearest_offset() needs pull_distance_field(nearest=True)")
+        ny, nx = self.nearest.shape[-2:]
+        iy = torch.arange(ny, dtype=torch.int32, device=self.nearest.device).view(1, ny, 1)
+        ix = torch.arange(nx, dtype=torch.int32, device=self.nearest.device).view(1, 1, nx)
+        have = self.nearest >= 0
+        n = torch.where(have, self.nearest, 0)
+        dy = torch.where(have, torch.div(n, nx, rounding_mode="floor") - iy, 0)
+        dx = torch.where(have, n % nx - ix, 0)
+        return torch.stack((dy, dx), -1).to(torch.int32)
+
+    def inflated_cost(self, inscribed_radius: float, inflation_radius: float, cost_scaling_factor: float = 10.0):
+        """uint8 [B, ny, nx] by the costmap convention (costmap_2d's inflation layer): 254 on an obstacle, 253 within
+        inscribed_radius of one, floor(252 exp(-cost_scaling_factor (d - inscribed_radius))) out to inflation_radius, 0 beyond;
+        radii and d in metres."""
+        import torch
+
+        r_ins, r_inf, k = float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor)
+        if not (0 <= r_ins <= r_inf < float("inf")) or not k >= 0:
+            raise ValueError("inflated_cost: 0 <= inscribed_radius <= inflation_radius, both finite; cost_scaling_factor >= 0")
+        d = self.distance()
+        cost = torch.floor(252.0 * torch.exp(-k * (d - r_ins)))
+        cost = torch.where(d <= r_ins, torch.full_like(cost, 253.0), cost)
+        cost = torch.where(self.dist2 == 0, torch.full_like(cost, 254.0), cost)
+        cost = torch.where(d > r_inf, torch.zeros_like(cost), cost)
+        return cost.to(torch.uint8)
+
+
+@dataclass
 class StatusStretchContacts:
     """New, without a reference counterpart (like `step` / `reset`): the contact list of every env's last physics step and its
     constraint forces -- what MuJoCo users read from MjData.contact and mj_contactForce after mj_step.  Every field is a device

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import math
 import os
 from typing import Optional, Sequence
 
@@ -22,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchHeightMap, StatusStretchJoints, StatusStretchOccupancyGrid, StatusStretchSensors
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchHeightMap, StatusStretchJoints, StatusStretchOccupancyGrid, StatusStretchSensors
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -143,6 +144,7 @@ class StretchBatchSimulator:
         self._depth_valid = set()   # depth cameras whose image has been rendered (pull_point_cloud(render=False) needs one)
         self._hmaps = {}            # (frame, (ny, nx)) -> the simulator-owned (height, count) of pull_height_map
         self._occ = {}              # (frame, (ny, nx)) -> the simulator-owned (hit, miss) of pull_occupancy_grid
+        self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
         self.xpose = torch.zeros(dims[D["NBODY"]] * 12, B, **f)
@@ -506,6 +508,82 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_lidar_to_occupancy")
         return StatusStretchOccupancyGrid(time=self.nstep.to(torch.float64) * self.timestep, hit=bufs[0], miss=bufs[1], origin=(x0, y0),
                                           cell=cell, frame=frame)
+
+    @_require_connection
+    def pull_distance_field(self, grid=None, *, min_hits: int = 1, unknown_is_obstacle: bool = False, max_distance=None,
+                            nearest: bool = False, cell=None, origin=None, **occupancy_kwargs) -> StatusStretchDistanceField:
+        """Exact Euclidean distance field of an occupancy grid in one HIP pass (smj_occupancy_to_distance, include/smj_distance.h):
+        per cell the squared distance in cells to the nearest obstacle cell (`dist2`) and, with nearest=True, that obstacle's linear
+        index, the smallest one among equally near obstacles.  Integers only: two calls give identical tensors.  New, without a
+        reference counterpart; StatusStretchDistanceField turns it into metres and an inflated costmap.
+
+        grid: None -- pull_occupancy_grid(**occupancy_kwargs) is called and transformed; a StatusStretchOccupancyGrid (a
+        world-frame map accumulated over steps, say), whose frame, origin and cell are taken over; or a bool / integer tensor
+        [B, ny, nx] of obstacles, e.g. pull_distance_field(hm.height > 0.10, cell=hm.cell, origin=hm.origin) -- then cell and origin
+        are these keywords (1.0 and (0, 0) if absent), min_hits is 1 and there is no miss layer.
+        A cell is an obstacle when hit >= min_hits, or, with unknown_is_obstacle, when no ray has seen it (hit == miss == 0).
+        max_distance (metres) bounds the search at R = ceil(max_distance / cell) cells: a cell further than R cells from every
+        obstacle gets StatusStretchDistanceField.NONE and -1, like every cell of a grid without obstacles.  None: no bound.
+        The tensors are simulator-owned and overwritten by the next call with the same shape."""
+        min_hits = int(min_hits)
+        if min_hits < 1:
+            raise ValueError("min_hits must be >= 1")
+        miss = None
+        if grid is None:
+            if cell is not None:
+                occupancy_kwargs["cell"] = cell
+            if origin is not None:
+                occupancy_kwargs["origin"] = origin
+            grid = self.pull_occupancy_grid(**occupancy_kwargs)
+            cell = origin = None
+        elif occupancy_kwargs:
+            raise ValueError(f"{sorted(occupancy_kwargs)}: keywords of pull_occupancy_grid, which is called only for grid=None")
+        if isinstance(grid, StatusStretchOccupancyGrid):
+            if cell is not None or origin is not None:
+                raise ValueError("cell and origin come from the StatusStretchOccupancyGrid")
+            hit, miss, frame, x0y0, cell = grid.hit, grid.miss, grid.frame, tuple(grid.origin), float(grid.cell)
+        else:
+            if not isinstance(grid, torch.Tensor) or grid.dtype not in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("grid: None, a StatusStretchOccupancyGrid, or a bool / integer tensor [B, ny, nx]")
+            if min_hits != 1 or unknown_is_obstacle:
+                raise ValueError("a mask has no counts and no miss layer: min_hits = 1, unknown_is_obstacle = False")
+            try:
+                x0y0 = (0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
+                cell = 1.0 if cell is None else float(cell)
+            except (TypeError, ValueError):
+                raise ValueError("origin = (x0, y0), cell a number") from None
+            if len(x0y0) != 2 or not (np.isfinite(x0y0[0]) and np.isfinite(x0y0[1])):
+                raise ValueError("origin = (x0, y0), finite")
+            hit, frame = (grid != 0).to(device=self.device, dtype=torch.int32).contiguous(), "grid"
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        for t in (hit, miss):
+            if t is not None and (t.dim() != 3 or t.shape[0] != self.num_envs or t.dtype != torch.int32 or not t.is_contiguous()
+                                  or t.device != self.device or (miss is not None and t.shape != hit.shape)):
+                raise ValueError(f"grid: contiguous int32 [num_envs = {self.num_envs}, ny, nx] on {self.device}")
+        ny, nx = int(hit.shape[1]), int(hit.shape[2])
+        if ny < 1 or nx < 1 or ny > 4096 or nx > 4096 or ny * nx > 65536:
+            raise ValueError("grid: 1 <= ny, nx <= 4096 and ny * nx <= 65536")
+        if unknown_is_obstacle and miss is None:
+            raise ValueError("unknown_is_obstacle needs a miss layer")
+        R = 0
+        if max_distance is not None:
+            max_distance = float(max_distance)
+            if not (np.isfinite(max_distance) and max_distance > 0):
+                raise ValueError("max_distance: metres, finite and > 0 (None = no bound)")
+            R = int(min(math.ceil(max_distance / cell), 8192))   # beyond the longest diagonal every bound is none
+        bufs = self._dist.get((ny, nx))
+        if bufs is None:
+            bufs = self._dist[(ny, nx)] = [torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device), None]
+        if nearest and bufs[1] is None:
+            bufs[1] = torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device)
+        near = bufs[1] if nearest else None
+        rc = self._L.smj_occupancy_to_distance(self._ctx, ctypes.c_void_p(hit.data_ptr()), ctypes.c_void_p(miss.data_ptr()) if miss is not None else None,
+                                               nx, ny, min_hits, int(bool(unknown_is_obstacle)), R, ctypes.c_void_p(bufs[0].data_ptr()),
+                                               ctypes.c_void_p(near.data_ptr()) if near is not None else None, self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_distance")
+        return StatusStretchDistanceField(time=self.nstep.to(torch.float64) * self.timestep, dist2=bufs[0], nearest=near, origin=x0y0, cell=cell,
+                                          frame=frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

@@ -1,4 +1,4 @@
-// THE TABLE OF STEP-KERNEL BUILDS.  The step kernel (smj_step_impl.h) is compiled 17 times, one translation unit each
+// THE TABLE OF STEP-KERNEL BUILDS.  The step kernel (smj_step_impl.h) is compiled 17 times (and once more as the lean twin of `step`, below), one translation unit each
 // (smj_kernels_<tag>.hip; build `step` lives in smj_kernels.hip).  A translation unit, the lane emulator's Makefiles and the host
 // tests select a build with SMJ_BUILD_TAG = <tag>; this header is the one place that says what the build is:
 //   * its FAMILY: the capacity macros smj_model.h / smj_sat_mem.h read (SMJ_TALL*, SMJ_BIG, SMJ_NVS, SMJ_SAT*, NCH), written once
@@ -83,6 +83,13 @@
 // first job of every step).  Same states bit for bit as `sat32` (option newton_two_waves = 0 selects that one).
 #define SMJ_ROW_sat32   SMJ_FAM_SAT32, SMJ_CARRIES_BOTH,   SMJ_CARRIES_BOTH,   1, 1, 0
 #define SMJ_ROW_sat32n  SMJ_FAM_SAT32, SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 2, 1, 0
+// The LEAN twin of `step` (smj_kernels_lean.hip): the same family, solver and wavefronts, with the paths a launch of the default model
+// with default options can never execute compiled out (SMJ_LEAN, smj_step_impl.h mcache_bound() .. nroot()) -- same arithmetic, same
+// results bit for bit, fewer registers held by dead code.  It is not a row the variant table routes to: smj_step swaps it in for `step`,
+// call by call, when smj_variants.h smj_lean_eligible says every folded predicate has its folded value; hand-over target, pollers and
+// sweep stay those of the standard variant.  Hence its own list: SMJ_BUILDS stays the set of builds smj_route chooses among.
+#define SMJ_LEAN_BUILDS(X) X(lean)
+#define SMJ_ROW_lean    SMJ_FAM_STD,   SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 1, 0, 0
 #define smj_step_kernel_step smj_step_kernel   // build `step` keeps the plain symbol names
 #define smj_launch_step_step smj_launch_step
 
@@ -211,4 +218,5 @@ enum SmjBuildId {
 };
 #define X(tag) extern const SmjBuildDesc smj_build_##tag;
 SMJ_BUILDS(X)
+SMJ_LEAN_BUILDS(X)
 #undef X

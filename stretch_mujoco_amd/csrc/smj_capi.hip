@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/smj.h"
+#include "../../include/smj_build.h"
 #include "smj_kernels.h"
 #include "smj_variants.h"
 #include "smj_model_load.h"
@@ -64,6 +65,8 @@ struct smj_ctx {
   int pipeline = 5;            // chunk length of the pipelined dispatch (DevState::pipe_len; 0 = one workgroup per env for the whole launch)
   bool pollers_always = false; // option "pollers" < 0: send the pollers with every launch (tests)
   bool prof_warned = false;    // the one-time warning of smj_step: profiling slot bound, the PGS kernel launched has no counters
+  int lean_build = 1;          // option "lean_build": 1 = a call that qualifies (smj_variants.h smj_lean_eligible) runs the lean twin of the standard Newton build, 0 = always the general build
+  const SmjBuildDesc* last_primary = nullptr;   // the primary build of the last smj_step (smj_last_build)
   int pollers = 2;             // tall-variant workgroups that finish parked envs beside the standard kernel (0: the sweep does it all)
   int* progress = nullptr;     // [B] progress, [B] done_steps, [SMJ_SCHED_WORDS] sched (DevState)
   size_t redo_cap = 0;         // entries the escalation list holds
@@ -309,6 +312,8 @@ const char* smj_version(void) { return "smj 0.1 (gfx950)"; }
 
 const char* smj_last_error(const smj_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+const char* smj_last_build(const smj_ctx* ctx) { return ctx && ctx->last_primary ? ctx->last_primary->tag : ""; }   // include/smj_build.h
+
 int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ctx** out) {
   if (!out) return -1;
   *out = nullptr;
@@ -525,7 +530,11 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   st.pipe_len = 0;
   st.pollers = 0;
   // which builds this call launches (the escalation model runs with the primary's options: one routing for both)
-  const SmjRoute route = smj_route(c->variant, c->model.solver, st.prof != nullptr, c->newton_two_waves, c->pgs_two_waves, smj_builds);
+  // (and the lean twin of the standard Newton build in its place when this call can execute none of what that twin leaves out)
+  const SmjLeanFacts lean_facts = smj_lean_facts(c->model, st, c->lean_build);
+  const SmjRoute route = smj_route_lean(smj_route(c->variant, c->model.solver, st.prof != nullptr, c->newton_two_waves, c->pgs_two_waves, smj_builds), lean_facts,
+                                        smj_builds[SMJ_B_step], &smj_build_lean);
+  c->last_primary = route.primary;
   int lrc = 0;
   for (int done = 0; done < nsteps && !lrc; done += chunk) {
     const int k = nsteps - done < chunk ? nsteps - done : chunk;
@@ -782,6 +791,7 @@ int smj_set_option(smj_ctx* c, const char* name, double v) {
   else if (!strcmp(name, "depth_raster_splits")) c->render.raster_splits = (int)(v < 1 ? 1 : v > 256 ? 256 : v);
   else if (!strcmp(name, "primary_rows")) m.row_limit = (int)v;   // the escalation variant keeps its full capacity (model_esc is not touched)
   else if (!strcmp(name, "escalate")) c->escalate = (int)v;
+  else if (!strcmp(name, "lean_build")) c->lean_build = (int)v;   // 0: every call runs the general build (A/B runs, tests); what qualifies a call for the lean one: smj_variants.h
   else if (!strcmp(name, "balance")) c->balance = (int)v;
   else if (!strcmp(name, "balance_min")) c->balance_min = (int)v;
   else if (!strcmp(name, "pgs_two_waves")) c->pgs_two_waves = (int)v;

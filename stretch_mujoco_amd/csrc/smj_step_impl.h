@@ -542,7 +542,7 @@ struct StepKernel {
   }
   SMJ_DEV void load_state() {
     const long ld = S.ld;
-    if (S.stage) {
+    if (staged()) {
       const float* st = stage_row();
       LANES {
         for (int k = lane; k < M.nq; k += 64) s.qpos[k] = ld_coh(&st[S.lay.qpos + k]);
@@ -573,7 +573,7 @@ struct StepKernel {
 #endif
     const int b = 1;  // base_link is the first body after the world
     const float bx = s.xpos[b][0], by = s.xpos[b][1], bth = atan2f(s.xmat[b][3], s.xmat[b][0]);
-    if (S.stage) {
+    if (staged()) {
       float* st = stage_row();
       int* sti = reinterpret_cast<int*>(st);
       LANES {
@@ -773,7 +773,7 @@ struct StepKernel {
       }
       for (int k = 0; k < 3; k++) xip[lane][k] = t[k];
     }
-    for (int r = 0; r < M.nroot; r++) {
+    for (int r = 0; r < nroot(); r++) {
       const int root = uni(M.k_root_list[r]);
       LANES {
         const bool in = lane > 0 && lane < nb && bt.root[lane] == root;
@@ -1142,7 +1142,7 @@ struct StepKernel {
       frc_act[lane] = v;
       g_r[lane] = frc_passive[lane] - frc_bias[lane] + frc_act[lane];
       if (lane < nv) s.g[lane] = g_r[lane];
-      if (dbg && S.debug && lane < nv) {
+      if (dbg && debug_bound() && lane < nv) {
         S.debug[(SMJ_DBG_QFRC_BIAS + lane) * S.ld + env] = frc_bias[lane];
         S.debug[(SMJ_DBG_QFRC_PASSIVE + lane) * S.ld + env] = frc_passive[lane];
         S.debug[(SMJ_DBG_QFRC_ACT + lane) * S.ld + env] = frc_act[lane];
@@ -2590,7 +2590,7 @@ struct StepKernel {
     float* mc = nullptr;
     const int ncon0 = ncon;
     // (not for capsule against capsule: a closed form, and its two contacts of the parallel case have normals of their own -- an entry keeps one)
-    if (S.mcache && M.manifold_cache && ta0 != GT_SPHERE && tb0 != GT_SPHERE && !(ta0 == GT_CAPSULE && tb0 == GT_CAPSULE)) {
+    if (mcache_bound() && manifold_cache() && ta0 != GT_SPHERE && tb0 != GT_SPHERE && !(ta0 == GT_CAPSULE && tb0 == GT_CAPSULE)) {
       mc = mc_entry(septag);
       const int b1 = uni(r[SMJ_CP_B1]), b2 = uni(r[SMJ_CP_B2]);
       PL<float> w;
@@ -3576,7 +3576,7 @@ struct StepKernel {
       if (lane < nv) { s.qacc[lane] = qacc_r[lane]; s.warm[lane] = qacc_r[lane]; s.tmp[lane] = g_r[lane] + qc[lane]; }
     }
     SYNC();
-    if (dbg && S.debug) {   // the debug layout holds the first 64 rows
+    if (dbg && debug_bound()) {   // the debug layout holds the first 64 rows
       LANES {
         if (lane < nv) S.debug[(SMJ_DBG_QACC + lane) * S.ld + env] = qacc_r[lane];
         S.debug[(SMJ_DBG_EFC_FORCE + lane) * S.ld + env] = lane < ne ? f_r[0][lane] : 0.f;
@@ -4616,7 +4616,7 @@ struct StepKernel {
 #if NSAT > 0
       SYNC();
 #endif
-      if (NSAT > 0 || M.nroot > 1) {
+      if (NSAT > 0 || nroot() > 1) {
         // scenes with free objects: the residual is re-evaluated from the new qacc with error-free transformations instead
         // of being advanced by alpha * jv.  jv = J search is a plain fp32 product (error ~1e-5 of terms that cancel to 1e-2),
         // and with D = 1/R up to 1e4 that is 0.1 N of force noise per iteration -- invisible on the 20 kg robot, 5 % of the
@@ -4650,7 +4650,7 @@ struct StepKernel {
 #endif
     }
     SYNC();
-    if (dbg && S.debug) {
+    if (dbg && debug_bound()) {
       LANES {
         if (lane < nv) S.debug[(SMJ_DBG_QACC + lane) * S.ld + env] = qacc[lane];
         const NRow& nr = nr0;   // the debug layout holds the first 64 rows
@@ -4759,7 +4759,7 @@ struct StepKernel {
 
   // IMU: gyro + accelerometer at the IMU site from the last forward pass  [MJ] mj_sensorVel / mj_sensorAcc
   SMJ_DEV void imu() {
-    if (M.imu_site < 0 || (!S.gyro && !S.stage)) return;
+    if (M.imu_site < 0 || (!S.gyro && !staged())) return;
     const int sid = M.imu_site, b = M.site_bodyid[sid];
     const uint64_t mk = mk64(M.k_body_dofmask_lo[b], M.k_body_dofmask_hi[b]);
     float cv[6], ca[6];
@@ -4787,7 +4787,7 @@ struct StepKernel {
     for (int k = 0; k < 3; k++) alin[k] += c2[k];
     mulmat3Tvec(gy, R, cv);
     mulmat3Tvec(ac, R, alin);
-    if (S.stage) {
+    if (staged()) {
       float* st = stage_row();
       LANES { if (lane < 3) { st[S.lay.gyro + lane] = gy[lane]; st[S.lay.accel + lane] = ac[lane]; } }
     } else {
@@ -4798,7 +4798,7 @@ struct StepKernel {
   // body poses of the last step for the ray-casting kernels (smj_render.hip: lidar, depth cameras): what mj_sensorPos /
   // mjv_updateScene read from mjData
   SMJ_DEV void dump_poses() {
-    if (S.stage) {   // contiguous: 12 words per body
+    if (staged()) {   // contiguous: 12 words per body
       float* st = stage_row() + S.lay.xpose;
       LANES {
         for (int k = lane; k < 12 * (M.nbody + M.nsat); k += 64) {
@@ -4817,7 +4817,7 @@ struct StepKernel {
     }
   }
   SMJ_DEV void dump_debug() {
-    if (!S.debug) return;
+    if (!debug_bound()) return;
     LANES {
       for (int i = 0; i < NVP; i++)
         if (lane < NVP) {
@@ -4837,7 +4837,7 @@ struct StepKernel {
     for (int k = 0; k < 9; k++) v[SMJ_CR_FRAME + k] = s.cframe[c][k];
   }
   SMJ_DEV void dump_contacts() {
-    if (!S.debug) return;
+    if (!debug_bound()) return;
     LANES {
       if (lane < NCON) {
         const int c = lane;
@@ -4891,6 +4891,25 @@ struct StepKernel {
 #else
   SMJ_DEV bool newton() const { return M.solver == 2; }
 #endif
+  // The same reasoning one level down: what a launch of the DEFAULT model with default options can never execute.  A translation unit
+  // that defines SMJ_LEAN (smj_kernels_lean.hip) turns the predicates below into constants, and the paths behind them -- kept manifolds,
+  // the debug dumps, the batch-major state, the exact residual of multi-root models -- leave the kernel with the registers
+  // they held.  Every other build reads the model / the state as before.  The host launches the lean build only for a call where every
+  // predicate has the folded value (smj_variants.h smj_lean_eligible); no live expression differs, so the two builds give the same bits.
+  // (The free-joint branches of kinematics and integration stay: the robot's own base is a free joint.)
+#if defined(SMJ_LEAN)
+  SMJ_DEV bool mcache_bound() const { return false; }
+  SMJ_DEV bool manifold_cache() const { return false; }
+  SMJ_DEV bool debug_bound() const { return false; }
+  SMJ_DEV bool staged() const { return true; }
+  SMJ_DEV int nroot() const { return 1; }
+#else
+  SMJ_DEV bool mcache_bound() const { return S.mcache != nullptr; }
+  SMJ_DEV bool manifold_cache() const { return M.manifold_cache != 0; }
+  SMJ_DEV bool debug_bound() const { return S.debug != nullptr; }
+  SMJ_DEV bool staged() const { return S.stage != nullptr; }
+  SMJ_DEV int nroot() const { return M.nroot; }
+#endif
   SMJ_DEV void run(int nsteps, unsigned read_flags) {
     const int want_imu = read_flags & 1;
     flags = 0; nefc = NEFC; ncon = 0; niter = 0;   // nefc = NEFC: the first make_constraint clears every row
@@ -4939,7 +4958,7 @@ struct StepKernel {
 #pragma nounroll
         for (int pass = 0; pass < 2; pass++) {
           collision_convex(pc, prof && pass == 0);
-          if (pass || !((flags & ~flags_planes) & SMJ_FLAG_CON_OVERFLOW) || !(SMJ_SPLIT_COLLIDE || (S.mcache && M.manifold_cache))) break;
+          if (pass || !((flags & ~flags_planes) & SMJ_FLAG_CON_OVERFLOW) || !(SMJ_SPLIT_COLLIDE || (mcache_bound() && manifold_cache()))) break;
           static_assert(SMJ_MC_SLOTS <= 64, "the redo clears the env's kept manifolds in ONE pass of the 64 lanes (SMJ_MC_LOG2 above 5 needs a loop here)");
           if (S.mcache) {
             LANES { if (lane < SMJ_MC_SLOTS) S.mcache[((size_t)env * SMJ_MC_SLOTS + lane) * SMJ_MC_WORDS] = 0.f; }
@@ -4968,7 +4987,7 @@ struct StepKernel {
 #if NSAT > 0
       if (newton()) solve_newton(last, pc, t0, prof);
       else solve_pgs_sat(last, pc, t0, prof);   // islands: the dense system + one lane per uncoupled satellite (smj_sat_pgs.h)
-      if (last && S.debug) {
+      if (last && debug_bound()) {
         LANES {
           if (lane >= 32 && lane - 32 < M.nsat)
             for (int k = 0; k < 6; k++) S.debug[(SMJ_DBG_SATQACC + 6 * (lane - 32) + k) * S.ld + env] = s.sat.x[SX_QA][lane - 32][k];

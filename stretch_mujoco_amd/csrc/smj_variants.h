@@ -68,3 +68,30 @@ static inline SmjRoute smj_route(int variant, int solver, bool prof_bound, int n
   }
   return r;
 }
+
+// ---- the lean twin of the standard variant's Newton build (smj_builds.h SMJ_ROW_lean, smj_step_impl.h SMJ_LEAN)
+// What smj_step knows of ONE call when it chooses between `step` and `lean`: the model's facts (DevModel::nroot), the options as they stand at this call (smj_set_option may have changed them since the last one) and the slots
+// bound now.  One field per predicate the lean build folds, plus the switch (option lean_build, default 1; 0: always the general build).
+struct SmjLeanFacts {
+  int nroot;            // tree roots of the model                         (folded: 1)
+  int manifold_cache;   // DevModel::manifold_cache as it stands           (folded: 0)
+  bool staged;          // the call runs on the staging rows (DevState::stage)   (folded: yes)
+  bool debug_bound;     // SMJ_SLOT_DEBUG is bound                         (folded: no)
+  bool prof_bound;      // SMJ_SLOT_PROF is bound: the caller asks for counters, the lean build has none
+  int lean_build;       // option lean_build
+};
+// (templates so that this header stays free of the model's and the state's definitions: Model = DevModel, State = DevState as the call launches it)
+template <class Model, class State>
+static inline SmjLeanFacts smj_lean_facts(const Model& m, const State& st, int lean_build) {
+  return SmjLeanFacts{m.nroot, m.manifold_cache, st.stage != nullptr, st.debug != nullptr, st.prof != nullptr, lean_build};
+}
+static inline bool smj_lean_eligible(const SmjLeanFacts& f) {
+  return f.lean_build != 0 && f.nroot == 1 && f.manifold_cache == 0 && f.staged && !f.debug_bound && !f.prof_bound;
+}
+// The route of a call with the lean twin swapped in where it may run: only for `general` (the standard variant's Newton build -- so
+// standard variant, Newton, no satellites, no profiling copy, by what smj_route chose) and only when every folded predicate holds.
+// Poller and sweep stay as routed: a step that runs out of rows is handed to the same target.
+static inline SmjRoute smj_route_lean(SmjRoute r, const SmjLeanFacts& f, const SmjBuildDesc* general, const SmjBuildDesc* lean) {
+  if (lean && r.primary == general && smj_lean_eligible(f)) r.primary = lean;
+  return r;
+}

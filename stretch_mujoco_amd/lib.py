@@ -25,6 +25,7 @@ POINT_EXPORTS = ("smj_depth_to_points",)   # include/smj_pointcloud.h (smj.h inc
 HEIGHTMAP_EXPORTS = ("smj_depth_to_heightmap",)   # include/smj_heightmap.h (smj.h includes it)
 OCCUPANCY_EXPORTS = ("smj_lidar_to_occupancy",)   # include/smj_occupancy.h (smj.h includes it)
 DISTANCE_EXPORTS = ("smj_occupancy_to_distance",)   # include/smj_distance.h (smj_occupancy.h includes it, so smj.h does)
+BUILD_EXPORTS = ("smj_last_build",)   # include/smj_build.h (a header of its own: smj.h does not include it)
 DIST_NONE = 1 << 30   # SMJ_DIST_NONE: dist2 of a cell with no obstacle in reach
 FRAME_CAMERA, FRAME_WORLD = -1, -2   # smj_depth_to_points: frame >= 0 is the frame of that fused body
 
@@ -96,6 +97,8 @@ def load() -> ctypes.CDLL:
     L.smj_last_error.argtypes = [vp]
     L.smj_last_error.restype = ctypes.c_char_p
     L.smj_version.restype = ctypes.c_char_p
+    L.smj_last_build.argtypes = [vp]
+    L.smj_last_build.restype = ctypes.c_char_p
     _lib = L
     return L
 

@@ -1,4 +1,4 @@
-"""Registers / scratch of every step-kernel variant in the built library: carves the gfx950 code objects out of libsmj.so's
+"""Registers / scratch / instruction counts of every step-kernel variant in the built library: carves the gfx950 code objects out of libsmj.so's
 fat binary (clang offload bundle: ELF images after the bundle header) and reads their metadata notes.  No GPU needed.
 Usage: python tools/kernel_resources.py [--digest] [path/to/libsmj.so]
 --digest: one line per kernel symbol of EVERY code object (not only the step kernels) with the SHA-256 of the kernel's machine code
@@ -47,6 +47,24 @@ def kernel_notes(image, d, n):
     return blocks
 
 
+def instruction_counts(d, n):
+    """{symbol: (instructions, v_writelane, v_readlane, branches)} of the code object kernel_notes wrote as co<n>.o, from its disassembly:
+    the size of a kernel in instructions, how many of them spill / reload a scalar register through a VGPR lane, and its branches."""
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", os.path.join(d, f"co{n}.o")], capture_output=True, text=True).stdout
+    counts, cur = {}, None
+    for line in out.split("\n"):
+        m = re.match(r"[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            cur = counts.setdefault(m.group(1), [0, 0, 0, 0])
+        elif cur is not None and "//" in line:
+            op = line.split()[0]
+            cur[0] += 1
+            cur[1] += op.startswith("v_writelane")
+            cur[2] += op.startswith("v_readlane")
+            cur[3] += op.startswith(("s_cbranch", "s_branch"))
+    return counts
+
+
 def symbol_bytes(image):
     """{symbol name: its bytes in the image} for every defined symbol with a size (functions, kernel descriptors)."""
     shoff, = struct.unpack_from("<Q", image, 0x28)
@@ -79,6 +97,7 @@ def main(so, digest=False):
         for n, image in enumerate(code_objects(blob)):
             syms = symbol_bytes(image) if digest else {}
             notes = kernel_notes(image, d, n)
+            icount = instruction_counts(d, n) if not digest and any("step_kernel" in k for k in notes) else {}
             if digest and notes:
                 rows.append(f"{min(notes)} (.text of its code object) {len(syms['.text'])} B sha256 {hashlib.sha256(syms['.text']).hexdigest()}")
             for name, blk in notes.items():
@@ -89,7 +108,8 @@ def main(so, digest=False):
                                 + " ".join(f"{k} {g(k)}" for k in DIGEST_META))
                 elif "step_kernel" in name:
                     rows.append(f"{name[:48]:48s} agpr {g('agpr_count'):>4s} vgpr {g('vgpr_count'):>4s} sgpr_spill {g('sgpr_spill_count'):>4s} "
-                                f"vgpr_spill {g('vgpr_spill_count'):>4s} scratch_bytes_per_lane {g('private_segment_fixed_size'):>5s}")
+                                f"vgpr_spill {g('vgpr_spill_count'):>4s} scratch_bytes_per_lane {g('private_segment_fixed_size'):>5s} "
+                                + "instructions {:6d} v_writelane {:5d} v_readlane {:5d} branches {:5d}".format(*icount.get(name, [0, 0, 0, 0])))
     for r in sorted(rows if digest else set(rows)):
         print(r)
 

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -124,6 +125,68 @@ static int alloc_zeroed(smj_ctx* c, size_t count, T** out) {
   c->allocs.push_back(d);
   HIPCHK(c, hipMemset(d, 0, sizeof(T) * count));
   *out = (T*)d;
+  return 0;
+}
+
+// ---- argument checks shared by the render and perception entries.  Each returns 0 or what fail() returned; an entry is a list of
+// them followed by a launch.  Order within an entry: -6 (the model has no tables) before every -1 (a bad argument) before -5 (a slot
+// is not bound), and nothing is allocated or launched before the last check has passed.
+#define TRY(call)             \
+  do {                        \
+    const int rc_ = (call);   \
+    if (rc_) return rc_;      \
+  } while (0)
+
+static int check_render_tables(smj_ctx* c, const char* consequence) {
+  return c->has_render ? 0 : fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*)%s", consequence);
+}
+
+static int check_camera_id(smj_ctx* c, int cam) {
+  return cam >= 0 && cam < c->render.ncam ? 0 : fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
+}
+
+// `what` names the arguments: the render entries have no stride (they pass 1)
+static int check_image(smj_ctx* c, int width, int height, int stride, float fovy_deg, const char* what) {
+  return width >= 1 && height >= 1 && stride >= 1 && fovy_deg > 0.f && fovy_deg < 180.f ? 0 : fail(c, -1, "bad %s", what);
+}
+
+// a frame argument (include/smj_pointcloud.h): SMJ_FRAME_CAMERA where the entry has a camera, SMJ_FRAME_WORLD, or a body id.  The
+// entries map the answer onto their kernels' own SMJ_PT_* / SMJ_OCC_* values.
+enum FrameKind { FRAME_IS_CAMERA, FRAME_IS_WORLD, FRAME_IS_BODY };
+static int check_frame(smj_ctx* c, int frame, bool camera_ok, FrameKind* kind) {
+  if (frame < SMJ_FRAME_WORLD || (frame == SMJ_FRAME_CAMERA && !camera_ok))
+    return fail(c, -1, "bad frame %d (%sSMJ_FRAME_WORLD or a body id)", frame, camera_ok ? "SMJ_FRAME_CAMERA, " : "");
+  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
+  *kind = frame == SMJ_FRAME_CAMERA ? FRAME_IS_CAMERA : frame == SMJ_FRAME_WORLD ? FRAME_IS_WORLD : FRAME_IS_BODY;
+  return 0;
+}
+
+static int check_grid(smj_ctx* c, int nx, int ny, int max_cells, float cell, float x0, float y0) {
+  if (nx < 1 || ny < 1 || (long long)nx * ny > max_cells) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, max_cells);
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  return 0;
+}
+
+// every buffer of an entry is read and written in 4-byte words (null pointers pass: whether one may be null is the entry's business)
+static int check_aligned(smj_ctx* c, std::initializer_list<const void*> ptrs, const char* what) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return bits & 3 ? fail(c, -1, "%s not aligned to 4 bytes", what) : 0;
+}
+
+static int check_xpose(smj_ctx* c) {
+  return c->state.xpose ? 0 : fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+}
+
+// device memory the context allocates at the first call that needs it and keeps (freed in smj_destroy)
+template <class T>
+static int ensure_alloc(smj_ctx* c, T** ptr, size_t bytes) {
+  if (*ptr) return 0;
+  void* d = nullptr;
+  HIPCHK(c, hipMalloc(&d, bytes));
+  c->allocs.push_back(d);
+  *ptr = (T*)d;
   return 0;
 }
 
@@ -622,28 +685,20 @@ int smj_base_controller_tick(smj_ctx* c, void* stream) {
 
 int smj_render_depth(smj_ctx* c, int cam, int width, int height, float fovy_deg, float max_depth, void* out_dev, void* stream) {
   if (!c) return -1;
-  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*)");
-  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
-  if (width <= 0 || height <= 0 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / field of view");
+  TRY(check_render_tables(c, ""));
+  TRY(check_camera_id(c, cam));
+  TRY(check_image(c, width, height, 1, fovy_deg, "image size / field of view"));
   if (!out_dev) return fail(c, -1, "null output image");
-  if (!c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->depth_ws) {
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, smj_depth_workspace_bytes(c->num_envs)));
-    c->allocs.push_back(d);
-    c->depth_ws = (float*)d;
-  }
+  TRY(ensure_alloc(c, &c->depth_ws, smj_depth_workspace_bytes(c->num_envs)));
   smj_ctx::Layer* L = nullptr;
   for (auto& l : c->layers)
     if (l.cam == cam && l.w == width && l.h == height && l.fovy == fovy_deg) L = &l;
   if (!L) {
     smj_ctx::Layer l;
     l.cam = cam; l.w = width; l.h = height; l.fovy = fovy_deg;
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(float) * (size_t)width * (size_t)height));
-    c->allocs.push_back(d);
-    l.buf = (float*)d;
+    TRY(ensure_alloc(c, &l.buf, sizeof(float) * (size_t)width * (size_t)height));
     smj_launch_depth(c->render, c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, cam, width, height, fovy_deg, 0.f, l.buf,
                      nullptr, 1, c->depth_ws, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
@@ -658,19 +713,14 @@ int smj_render_depth(smj_ctx* c, int cam, int width, int height, float fovy_deg,
 
 int smj_render_rgb(smj_ctx* c, int cam, int width, int height, float fovy_deg, void* rgb_dev, void* gid_dev, void* stream) {
   if (!c) return -1;
-  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*)");
+  TRY(check_render_tables(c, ""));
   if (!c->render.geom_rgba) return fail(c, -6, "the model blob carries no geom colours (geom_rgba)");
-  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
-  if (width <= 0 || height <= 0 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / field of view");
+  TRY(check_camera_id(c, cam));
+  TRY(check_image(c, width, height, 1, fovy_deg, "image size / field of view"));
   if (!rgb_dev) return fail(c, -1, "null output image");
-  if (!c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->depth_ws) {
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, smj_depth_workspace_bytes(c->num_envs)));
-    c->allocs.push_back(d);
-    c->depth_ws = (float*)d;
-  }
+  TRY(ensure_alloc(c, &c->depth_ws, smj_depth_workspace_bytes(c->num_envs)));
   smj_launch_rgb(c->render, c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, cam, width, height, fovy_deg,
                  (unsigned char*)rgb_dev, (int*)gid_dev, c->depth_ws, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
@@ -680,24 +730,19 @@ int smj_render_rgb(smj_ctx* c, int cam, int width, int height, float fovy_deg, v
 int smj_depth_to_points(smj_ctx* c, int cam, int width, int height, float fovy_deg, const void* depth_dev, int stride, int frame,
                         void* points_dev, void* stream) {
   if (!c) return -1;
-  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*): no cameras");
-  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
-  if (width < 1 || height < 1 || stride < 1 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / stride / field of view");
+  FrameKind fk;
+  TRY(check_render_tables(c, ": no cameras"));
+  TRY(check_camera_id(c, cam));
+  TRY(check_image(c, width, height, stride, fovy_deg, "image size / stride / field of view"));
   if (!depth_dev || !points_dev) return fail(c, -1, "null depth image / point buffer");
-  if (((uintptr_t)depth_dev | (uintptr_t)points_dev) & 3) return fail(c, -1, "depth image / point buffer not aligned to 4 bytes");
-  if (frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_CAMERA, SMJ_FRAME_WORLD or a body id)", frame);
-  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
+  TRY(check_aligned(c, {depth_dev, points_dev}, "depth image / point buffer"));
+  TRY(check_frame(c, frame, true, &fk));
   const long long per_env = (long long)smj_points_grid(width, stride) * smj_points_grid(height, stride);
   if (per_env > 0x7fffffffLL || per_env * c->num_envs > 0x7fffffffLL * 1024) return fail(c, -1, "point grid too large");
-  if (frame != SMJ_FRAME_CAMERA && !c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  if (fk != FRAME_IS_CAMERA) TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->points_ws) {
-    void* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, smj_points_workspace_bytes(c->num_envs)));
-    c->allocs.push_back(d);
-    c->points_ws = (float*)d;
-  }
-  const int kind = frame == SMJ_FRAME_CAMERA ? SMJ_PT_CAMERA : frame == SMJ_FRAME_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
+  TRY(ensure_alloc(c, &c->points_ws, smj_points_workspace_bytes(c->num_envs)));
+  const int kind = fk == FRAME_IS_CAMERA ? SMJ_PT_CAMERA : fk == FRAME_IS_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
   smj_launch_points(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam,
                     width, height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, (float*)points_dev,
                     c->points_ws, (hipStream_t)stream);
@@ -709,21 +754,19 @@ int smj_depth_to_heightmap(smj_ctx* c, int cam, int width, int height, float fov
                            float x0, float y0, float cell, int nx, int ny, float z_lo, float z_hi, int accumulate, void* zmax_dev,
                            void* count_dev, void* stream) {
   if (!c) return -1;
-  if (!c->has_render) return fail(c, -6, "the model blob carries no render tables (k_rgeom / rmesh_*): no cameras");
-  if (cam < 0 || cam >= c->render.ncam) return fail(c, -1, "camera id %d out of range (ncam %d)", cam, c->render.ncam);
-  if (width < 1 || height < 1 || stride < 1 || !(fovy_deg > 0.f && fovy_deg < 180.f)) return fail(c, -1, "bad image size / stride / field of view");
+  FrameKind fk;
+  TRY(check_render_tables(c, ": no cameras"));
+  TRY(check_camera_id(c, cam));
+  TRY(check_image(c, width, height, stride, fovy_deg, "image size / stride / field of view"));
   if ((long long)width * height > 0x7fffffffLL) return fail(c, -1, "image too large");
-  if (nx < 1 || ny < 1 || (long long)nx * ny > SMJ_HMAP_MAX_CELLS) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, (int)SMJ_HMAP_MAX_CELLS);
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  TRY(check_grid(c, nx, ny, SMJ_HMAP_MAX_CELLS, cell, x0, y0));
   if (!(z_lo <= z_hi)) return fail(c, -1, "bad height band (NaN, or z_lo > z_hi)");
   if (!depth_dev || !zmax_dev) return fail(c, -1, "null depth image / height buffer");
-  if (((uintptr_t)depth_dev | (uintptr_t)zmax_dev | (uintptr_t)count_dev) & 3) return fail(c, -1, "depth image / height / count buffer not aligned to 4 bytes");
-  if (frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_CAMERA, SMJ_FRAME_WORLD or a body id)", frame);
-  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
-  if (frame != SMJ_FRAME_CAMERA && !c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  TRY(check_aligned(c, {depth_dev, zmax_dev, count_dev}, "depth image / height / count buffer"));
+  TRY(check_frame(c, frame, true, &fk));
+  if (fk != FRAME_IS_CAMERA) TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  const int kind = frame == SMJ_FRAME_CAMERA ? SMJ_PT_CAMERA : frame == SMJ_FRAME_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
+  const int kind = fk == FRAME_IS_CAMERA ? SMJ_PT_CAMERA : fk == FRAME_IS_WORLD ? SMJ_PT_WORLD : SMJ_PT_BODY;
   smj_launch_hmap(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.cam_bodyid, c->render.cam_pos, c->render.cam_mat, cam, width,
                   height, fovy_deg, (const float*)depth_dev, stride, kind, kind == SMJ_PT_BODY ? frame : 0, x0, y0, cell, nx, ny, z_lo, z_hi,
                   accumulate != 0, (float*)zmax_dev, (int*)count_dev, (hipStream_t)stream);
@@ -734,20 +777,18 @@ int smj_depth_to_heightmap(smj_ctx* c, int cam, int width, int height, float fov
 int smj_lidar_to_occupancy(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame, float x0, float y0, float cell, int nx, int ny,
                            float r_min, float r_max, int no_return_clears, int accumulate, void* hit_dev, void* miss_dev, void* stream) {
   if (!c) return -1;
+  FrameKind fk;
   if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to map");
   if (!lidar_dev || !hit_dev) return fail(c, -1, "null scan / hit buffer");
-  if (((uintptr_t)lidar_dev | (uintptr_t)hit_dev | (uintptr_t)miss_dev) & 3) return fail(c, -1, "scan / hit / miss buffer not aligned to 4 bytes");
+  TRY(check_aligned(c, {lidar_dev, hit_dev, miss_dev}, "scan / hit / miss buffer"));
   if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
-  if (nx < 1 || ny < 1 || (long long)nx * ny > SMJ_OCC_MAX_CELLS) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, (int)SMJ_OCC_MAX_CELLS);
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  TRY(check_grid(c, nx, ny, SMJ_OCC_MAX_CELLS, cell, x0, y0));
   if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
   if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d: a ray would cross more cells than the line arithmetic takes", (int)SMJ_OCC_MAX_STEPS);
-  if (frame == SMJ_FRAME_CAMERA || frame < SMJ_FRAME_WORLD) return fail(c, -1, "bad frame %d (SMJ_FRAME_WORLD or a body id)", frame);
-  if (frame >= c->model.nbody_all) return fail(c, -1, "frame: body id %d out of range (nbody %d)", frame, c->model.nbody_all);
-  if (!c->state.xpose) return fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+  TRY(check_frame(c, frame, false, &fk));
+  TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  const int kind = frame == SMJ_FRAME_WORLD ? SMJ_OCC_WORLD : SMJ_OCC_BODY;
+  const int kind = fk == FRAME_IS_WORLD ? SMJ_OCC_WORLD : SMJ_OCC_BODY;
   smj_launch_occ(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.nlidar, c->render.lidar_site, c->render.site_bodyid,
                  c->render.site_pos, c->render.site_mat, (const float*)lidar_dev, lidar_ld, kind, kind == SMJ_OCC_BODY ? frame : 0, x0, y0, cell,
                  nx, ny, r_min, r_max, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (hipStream_t)stream);
@@ -759,7 +800,7 @@ int smj_occupancy_to_distance(smj_ctx* c, const void* hit_dev, const void* miss_
                               int max_dist_cells, void* dist2_dev, void* nearest_dev, void* stream) {
   if (!c) return -1;
   if (!hit_dev || !dist2_dev) return fail(c, -1, "null hit / dist2 buffer");
-  if (((uintptr_t)hit_dev | (uintptr_t)miss_dev | (uintptr_t)dist2_dev | (uintptr_t)nearest_dev) & 3) return fail(c, -1, "hit / miss / dist2 / nearest buffer not aligned to 4 bytes");
+  TRY(check_aligned(c, {hit_dev, miss_dev, dist2_dev, nearest_dev}, "hit / miss / dist2 / nearest buffer"));
   if (nx < 1 || ny < 1 || nx > SMJ_EDT_MAX_SIDE || ny > SMJ_EDT_MAX_SIDE || (long long)nx * ny > SMJ_EDT_MAX_CELLS)
     return fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, (int)SMJ_EDT_MAX_SIDE, (int)SMJ_EDT_MAX_CELLS);
   if (min_hits < 1) return fail(c, -1, "min_hits %d below 1: every cell would be an obstacle", min_hits);

@@ -84,6 +84,22 @@ SMJ_PT_HD int smj_hmap_slot(smj_hmap_band_t b, int ix, int iy) {
   return r < (unsigned)b.rows && c < (unsigned)b.cols ? (int)(r * (unsigned)b.cols + c) : -1;
 }
 
+// The store of a band of ncell 4-byte cells to the address `out` (4-byte aligned): `lead` single cells up to the first 16-byte
+// boundary, `groups` groups of four cells from there (16-byte stores), and the tail from cell tail0 on.  The `rest` = lead + tail
+// single cells (at most 6) are numbered t = 0 .. rest - 1 by smj_hmap_split_rest.  Every cell is stored exactly once.
+struct smj_hmap_split_t { int lead, groups, tail0, rest; };
+
+SMJ_PT_HD smj_hmap_split_t smj_hmap_store_split(uintptr_t out, int ncell) {
+  smj_hmap_split_t s;
+  s.lead = (int)((16u - (unsigned)(out & 15u)) & 15u) >> 2;
+  if (s.lead > ncell) s.lead = ncell;
+  s.groups = (ncell - s.lead) >> 2;
+  s.tail0 = s.lead + 4 * s.groups;
+  s.rest = s.lead + (ncell - s.tail0);
+  return s;
+}
+SMJ_PT_HD int smj_hmap_split_rest(smj_hmap_split_t s, int t) { return t < s.lead ? t : s.tail0 + (t - s.lead); }
+
 #if defined(__HIPCC__)
 // Launch (smj_hmap.hip).  kind / body as smj_launch_points; count may be null.
 void smj_launch_hmap(const float* xpose, long ld, int num_envs, const int* cam_bodyid, const float* cam_pos, const float* cam_mat,

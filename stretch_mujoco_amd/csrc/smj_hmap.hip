@@ -71,17 +71,8 @@ __global__ __launch_bounds__(HM_THREADS) void smj_hmap_kernel(const HmapArgs a) 
 
   // (1) transform and start values
   if (tid == 0) {
-    float cbp[3] = {}, cbm[9] = {}, bp[3] = {}, bm[9] = {}, T[12];
-    if (a.kind != SMJ_PT_CAMERA) {
-      const int cb = a.cam_bodyid[a.cam];
-      for (int k = 0; k < 3; k++) cbp[k] = a.xpose[(12 * cb + k) * a.ld + env];
-      for (int k = 0; k < 9; k++) cbm[k] = a.xpose[(12 * cb + 3 + k) * a.ld + env];
-      if (a.kind == SMJ_PT_BODY) {
-        for (int k = 0; k < 3; k++) bp[k] = a.xpose[(12 * a.body + k) * a.ld + env];
-        for (int k = 0; k < 9; k++) bm[k] = a.xpose[(12 * a.body + 3 + k) * a.ld + env];
-      }
-    }
-    smj_points_transform(a.kind, cbp, cbm, a.cam_pos + 3 * a.cam, a.cam_mat + 9 * a.cam, bp, bm, T);
+    float T[12];
+    smj_points_env_transform(a.kind, a.xpose, a.ld, env, a.cam_bodyid, a.cam_pos, a.cam_mat, a.cam, a.body, T);
     for (int k = 0; k < 12; k++) Ts[k] = T[k];
   }
   __syncthreads();
@@ -149,21 +140,18 @@ __global__ __launch_bounds__(HM_THREADS) void smj_hmap_kernel(const HmapArgs a) 
   __syncthreads();
 
   // (3) decode and store the band once: scalar cells up to the first 16-byte boundary of the output, groups of four, the tail
-  int lead = (int)((16u - (unsigned)((uintptr_t)zo & 15u)) & 15u) >> 2;
-  if (lead > ncell) lead = ncell;
-  const int ng = (ncell - lead) >> 2, tail0 = lead + 4 * ng;
+  const smj_hmap_split_t s = smj_hmap_store_split((uintptr_t)zo, ncell);
   const bool cvec = co && (((uintptr_t)co ^ (uintptr_t)zo) & 15u) == 0;   // the counts share the heights' phase: wide stores for both
-  for (int g = tid; g < ng; g += HM_THREADS) {
-    const int c = lead + 4 * g;
+  for (int g = tid; g < s.groups; g += HM_THREADS) {
+    const int c = s.lead + 4 * g;
     *reinterpret_cast<float4*>(zo + c) =
         make_float4(smj_hmap_unkey(keys[c]), smj_hmap_unkey(keys[c + 1]), smj_hmap_unkey(keys[c + 2]), smj_hmap_unkey(keys[c + 3]));
     if (cvec) *reinterpret_cast<int4*>(co + c) = make_int4((int)cnt[c], (int)cnt[c + 1], (int)cnt[c + 2], (int)cnt[c + 3]);
   }
   if (co && !cvec)
-    for (int c = lead + tid; c < tail0; c += HM_THREADS) co[c] = (int)cnt[c];
-  const int nrest = lead + (ncell - tail0);
-  if (tid < nrest) {
-    const int c = tid < lead ? tid : tail0 + (tid - lead);
+    for (int c = s.lead + tid; c < s.tail0; c += HM_THREADS) co[c] = (int)cnt[c];
+  if (tid < s.rest) {
+    const int c = smj_hmap_split_rest(s, tid);
     zo[c] = smj_hmap_unkey(keys[c]);
     if (co) co[c] = (int)cnt[c];
   }

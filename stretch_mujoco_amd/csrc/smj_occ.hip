@@ -56,18 +56,15 @@ struct OccArgs {
   float x0, y0, inv_cell, r_min, r_max;
 };
 
-// lead scalar cells up to the first 16-byte boundary, groups of four, the tail: the store of smj_hmap.hip for one int32 array
+// one int32 array of the band, by the split of smj_hmap.h: lead cells, groups of four, the tail
 __device__ __forceinline__ void occ_store(int* out, const unsigned* src, int ncell, int tid) {
-  int lead = (int)((16u - (unsigned)((uintptr_t)out & 15u)) & 15u) >> 2;
-  if (lead > ncell) lead = ncell;
-  const int ng = (ncell - lead) >> 2, tail0 = lead + 4 * ng;
-  for (int g = tid; g < ng; g += OCC_THREADS) {
-    const int c = lead + 4 * g;
+  const smj_hmap_split_t s = smj_hmap_store_split((uintptr_t)out, ncell);
+  for (int g = tid; g < s.groups; g += OCC_THREADS) {
+    const int c = s.lead + 4 * g;
     *reinterpret_cast<int4*>(out + c) = make_int4((int)src[c], (int)src[c + 1], (int)src[c + 2], (int)src[c + 3]);
   }
-  const int nrest = lead + (ncell - tail0);   // <= 6 cells
-  if (tid < nrest) {
-    const int c = tid < lead ? tid : tail0 + (tid - lead);
+  if (tid < s.rest) {   // <= 6 cells
+    const int c = smj_hmap_split_rest(s, tid);
     out[c] = (int)src[c];
   }
 }

@@ -97,6 +97,23 @@ SMJ_PT_HD void smj_points_transform(int kind, const float* cbp, const float* cbm
   }
 }
 
+// Pose (p, m) of fused body `body` of env `env` from XPOSE, [nbody * 12][ld] batch-major: position, then the row-major 3x3
+SMJ_PT_HD void smj_xpose_body(const float* xpose, long ld, int env, int body, float* p, float* m) {
+  for (int k = 0; k < 3; k++) p[k] = xpose[(12 * body + k) * ld + env];
+  for (int k = 0; k < 9; k++) m[k] = xpose[(12 * body + 3 + k) * ld + env];
+}
+
+// smj_points_transform for env `env` of camera `cam`, with the poses it needs read from XPOSE (none for SMJ_PT_CAMERA)
+SMJ_PT_HD void smj_points_env_transform(int kind, const float* xpose, long ld, int env, const int* cam_bodyid, const float* cam_pos,
+                                        const float* cam_mat, int cam, int body, float* T) {
+  float cbp[3] = {}, cbm[9] = {}, bp[3] = {}, bm[9] = {};
+  if (kind != SMJ_PT_CAMERA) {
+    smj_xpose_body(xpose, ld, env, cam_bodyid[cam], cbp, cbm);
+    if (kind == SMJ_PT_BODY) smj_xpose_body(xpose, ld, env, body, bp, bm);
+  }
+  smj_points_transform(kind, cbp, cbm, cam_pos + 3 * cam, cam_mat + 9 * cam, bp, bm, T);
+}
+
 #if defined(__HIPCC__)
 // Launches (smj_points.hip).  workspace: smj_points_workspace_bytes(num_envs) of device memory, the per-env transforms.
 // kind / body: SMJ_PT_* and, for SMJ_PT_BODY, the fused body; xpose [nbody*12][ld] batch-major (not read for SMJ_PT_CAMERA).

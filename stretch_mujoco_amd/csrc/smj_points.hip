@@ -16,17 +16,8 @@ __global__ __launch_bounds__(64) void smj_points_prepass(const float* __restrict
                                                          int body, float* __restrict__ ws) {
   const int env = blockIdx.x * 64 + threadIdx.x;   // lane = env: the batch-major pose reads are contiguous across the wavefront
   if (env >= num_envs) return;
-  float cbp[3] = {}, cbm[9] = {}, bp[3] = {}, bm[9] = {}, T[12];
-  if (kind != SMJ_PT_CAMERA) {
-    const int cb = cam_bodyid[cam];
-    for (int k = 0; k < 3; k++) cbp[k] = xpose[(12 * cb + k) * ld + env];
-    for (int k = 0; k < 9; k++) cbm[k] = xpose[(12 * cb + 3 + k) * ld + env];
-    if (kind == SMJ_PT_BODY) {
-      for (int k = 0; k < 3; k++) bp[k] = xpose[(12 * body + k) * ld + env];
-      for (int k = 0; k < 9; k++) bm[k] = xpose[(12 * body + 3 + k) * ld + env];
-    }
-  }
-  smj_points_transform(kind, cbp, cbm, cam_pos + 3 * cam, cam_mat + 9 * cam, bp, bm, T);
+  float T[12];
+  smj_points_env_transform(kind, xpose, ld, env, cam_bodyid, cam_pos, cam_mat, cam, body, T);
   for (int k = 0; k < 12; k++) ws[12 * (long)env + k] = T[k];
 }
 

@@ -269,14 +269,13 @@ class StretchBatchSimulator:
 
     @_require_connection
     def pull_status(self) -> StatusStretchJoints:
-        time = self.nstep.to(torch.float64) * self.timestep
-        return Glue.pull_status(time, self.actuator_length, self.actuator_velocity, self.base_pose)
+        return Glue.pull_status(self._time(), self.actuator_length, self.actuator_velocity, self.base_pose)
 
     @_require_connection
     def pull_sensor_data(self) -> StatusStretchSensors:
         """gyro [B,3], accel (field base_imu) [B,3], lidar [B,360]; values of the last physics step of the last launch.
         The reference refreshes these at 15 Hz wall clock (mujoco_server.py:271); here the cadence is the caller's step(n)."""
-        out = StatusStretchSensors(time=self.nstep.to(torch.float64) * self.timestep, fps=0.0)
+        out = StatusStretchSensors(time=self._time(), fps=0.0)
         if self._read_flags & _lib.READ_IMU:
             out.base_gyro = self.gyro.t().clone()
             out.base_imu = self.accel.t().clone()
@@ -294,18 +293,13 @@ class StretchBatchSimulator:
         The image tensors are simulator-owned and overwritten by the next call."""
         from .utils import compute_K
 
-        out = StatusStretchCameras(time=self.nstep.to(torch.float64) * self.timestep, fps=0.0)
-        names = self.names["camera"]
+        out = StatusStretchCameras(time=self._time(), fps=0.0)
         for cam in self._cameras:
-            st = cam.initial_camera_settings
-            img = self._depth[cam]
             if cam.is_depth:
-                self._render_depth_into(cam, img)
-                self._depth_valid.add(cam)
+                img = self._depth_image(cam, True)
             else:
-                rc = self._L.smj_render_rgb(self._ctx, names.index(cam.camera_name_in_mjcf), st.width, st.height,
-                                            float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), None,
-                                            self._stream())
+                img = self._depth[cam]
+                rc = self._L.smj_render_rgb(self._ctx, *self._camera_args(cam), ctypes.c_void_p(img.data_ptr()), None, self._stream())
                 _lib.check(self._L, self._ctx, rc, "smj_render_rgb")
             out.set_camera_data(cam, img)
         for attr, cam in (("cam_d405_K", StretchCameras.cam_d405_rgb), ("cam_d435i_K", StretchCameras.cam_d435i_rgb)):
@@ -313,12 +307,71 @@ class StretchBatchSimulator:
             setattr(out, attr, compute_K(st.field_of_view_vertical_in_degrees, st.sensor_resolution[0], st.sensor_resolution[1]))
         return out
 
-    def _render_depth_into(self, cam, img) -> None:
+    # ------------------------------------------------------------------ shared by the pull_* of the perception entries
+    def _time(self) -> torch.Tensor:
+        return self.nstep.to(torch.float64) * self.timestep
+
+    def _camera_args(self, cam):
+        """(index, width, height, fovy): the leading arguments of every C entry that takes a camera."""
         st = cam.initial_camera_settings
-        rc = self._L.smj_render_depth(self._ctx, self.names["camera"].index(cam.camera_name_in_mjcf), st.width, st.height,
-                                      float(st.field_of_view_vertical_in_degrees), cam.depth_limit,
-                                      ctypes.c_void_p(img.data_ptr()), self._stream())
+        return self.names["camera"].index(cam.camera_name_in_mjcf), st.width, st.height, float(st.field_of_view_vertical_in_degrees)
+
+    def _render_depth_into(self, cam, img) -> None:
+        rc = self._L.smj_render_depth(self._ctx, *self._camera_args(cam), cam.depth_limit, ctypes.c_void_p(img.data_ptr()), self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_render_depth")
+
+    def _depth_image(self, cam, render: bool) -> torch.Tensor:
+        """The camera's depth image: rendered now (and marked valid), or the one of an earlier call, which there must have been."""
+        img = self._depth[cam]
+        if render:
+            self._render_depth_into(cam, img)
+            self._depth_valid.add(cam)
+        elif cam not in self._depth_valid:
+            raise _lib.SmjError(f"render=False: {cam.name} has not been rendered yet (pull_camera_data() or pull_point_cloud() first)")
+        return img
+
+    def _base_frame(self):
+        """(fused body base_link lives in, its fixed pose there as (r, R) or None where that pose is the identity)."""
+        i = self.names["body"].index("base_link")
+        rp = np.asarray(self.model["link_relpos"][i], np.float64)
+        Rl = self._quat_mat(self.model["link_relquat"][i], self.device)
+        identity = not np.any(rp != 0) and torch.equal(Rl, torch.eye(3, device=self.device))
+        return int(self.model["link_fused"][i]), None if identity else (torch.tensor(rp, dtype=torch.float32, device=self.device), Rl)
+
+    def _frame_id(self, frame, allowed):
+        """Frame name -> (the C entries' frame id, base_link's fixed offset inside that body or None)."""
+        if frame not in allowed:
+            quoted = [f'"{a}"' for a in allowed]
+            raise ValueError(f'frame must be {", ".join(quoted[:-1])} or {quoted[-1]}')
+        if frame == "base":
+            return self._base_frame()
+        return (_lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD), None
+
+    @staticmethod
+    def _grid_args(shape, origin, cell, pair, pair_doc):
+        """(ny, nx, x0, y0, cell, lo, hi) of a binned map, checked; `pair` is the entry's own interval (z_range, range_limits)."""
+        try:
+            ny, nx = (int(v) for v in shape)
+            x0, y0 = (float(v) for v in origin)
+            lo, hi = (float(v) for v in pair)
+        except (TypeError, ValueError):
+            raise ValueError(f"shape = (ny, nx), origin = (x0, y0), {pair_doc}") from None
+        if ny < 1 or nx < 1 or ny * nx > 65536:
+            raise ValueError("shape: ny, nx >= 1 and ny * nx <= 65536")
+        cell = float(cell)
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        if not (np.isfinite(x0) and np.isfinite(y0)):
+            raise ValueError("origin must be finite")
+        return ny, nx, x0, y0, cell, lo, hi
+
+    @staticmethod
+    def _cached(cache, key, make):
+        """The simulator-owned buffers of `key`, made on first use."""
+        bufs = cache.get(key)
+        if bufs is None:
+            bufs = cache[key] = make()
+        return bufs
 
     @_require_connection
     def pull_point_cloud(self, camera: StretchCameras, frame: str = "camera", stride: int = 1, render: bool = True,
@@ -338,35 +391,15 @@ class StretchBatchSimulator:
         the xyz values are untouched.  The tensor is simulator-owned and overwritten by the next call with the same (camera, stride)."""
         if not isinstance(camera, StretchCameras) or not camera.is_depth or camera not in self._cameras:
             raise ValueError(f"{camera} is not a depth camera of cameras_to_use")
-        if frame not in ("camera", "world", "base"):
-            raise ValueError('frame must be "camera", "world" or "base"')
+        fr, offset = self._frame_id(frame, ("camera", "world", "base"))
         stride = int(stride)
         if stride < 1:
             raise ValueError("stride must be >= 1")
         st = camera.initial_camera_settings
-        img = self._depth[camera]
-        if render:
-            self._render_depth_into(camera, img)
-            self._depth_valid.add(camera)
-        elif camera not in self._depth_valid:
-            raise _lib.SmjError(f"render=False: {camera.name} has not been rendered yet (pull_camera_data() or pull_point_cloud() first)")
-        key = (camera, stride)
-        pts = self._points.get(key)
-        if pts is None:
-            pts = self._points[key] = torch.zeros(self.num_envs, -(-st.height // stride), -(-st.width // stride), 3,
-                                                  dtype=torch.float32, device=self.device)
-        offset = None
-        if frame == "base":
-            i = self.names["body"].index("base_link")
-            fr = int(self.model["link_fused"][i])      # the fused body base_link lives in, and its fixed pose there
-            rp = np.asarray(self.model["link_relpos"][i], np.float64)
-            Rl = self._quat_mat(self.model["link_relquat"][i], self.device)
-            if np.any(rp != 0) or not torch.equal(Rl, torch.eye(3, device=self.device)):
-                offset = (torch.tensor(rp, dtype=torch.float32, device=self.device), Rl)
-        else:
-            fr = _lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD
-        rc = self._L.smj_depth_to_points(self._ctx, self.names["camera"].index(camera.camera_name_in_mjcf), st.width, st.height,
-                                         float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), stride, fr,
+        img = self._depth_image(camera, render)
+        pts = self._cached(self._points, (camera, stride), lambda: torch.zeros(
+            self.num_envs, -(-st.height // stride), -(-st.width // stride), 3, dtype=torch.float32, device=self.device))
+        rc = self._L.smj_depth_to_points(self._ctx, *self._camera_args(camera), ctypes.c_void_p(img.data_ptr()), stride, fr,
                                          ctypes.c_void_p(pts.data_ptr()), self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_depth_to_points")
         if offset is not None:
@@ -400,56 +433,29 @@ class StretchBatchSimulator:
         for c in cams:
             if not isinstance(c, StretchCameras) or c not in depth_cams:
                 raise ValueError(f"{c} is not a depth camera of cameras_to_use")
-        if frame not in ("camera", "world", "base"):
-            raise ValueError('frame must be "camera", "world" or "base"')
-        try:
-            ny, nx = (int(v) for v in shape)
-            x0, y0 = (float(v) for v in origin)
-            lo, hi = (float(v) for v in z_range)
-        except (TypeError, ValueError):
-            raise ValueError("shape = (ny, nx), origin = (x0, y0), z_range = (lo, hi)") from None
-        if ny < 1 or nx < 1 or ny * nx > 65536:
-            raise ValueError("shape: ny, nx >= 1 and ny * nx <= 65536")
-        cell = float(cell)
-        if not (np.isfinite(cell) and cell > 0):
-            raise ValueError("cell must be finite and > 0")
-        if not (np.isfinite(x0) and np.isfinite(y0)):
-            raise ValueError("origin must be finite")
+        fr, offset = self._frame_id(frame, ("camera", "world", "base"))
+        ny, nx, x0, y0, cell, lo, hi = self._grid_args(shape, origin, cell, z_range, "z_range = (lo, hi)")
         if not lo <= hi:
             raise ValueError("z_range: lo <= hi, neither NaN")
         stride = int(stride)
         if stride < 1:
             raise ValueError("stride must be >= 1")
-        if frame == "base":
-            i = self.names["body"].index("base_link")
-            fr = int(self.model["link_fused"][i])
-            if np.any(np.asarray(self.model["link_relpos"][i], np.float64) != 0) or not torch.equal(
-                    self._quat_mat(self.model["link_relquat"][i], self.device), torch.eye(3, device=self.device)):
-                raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned map cannot be '
-                                 'corrected afterwards (use frame="world", or pull_point_cloud)')
-        else:
-            fr = _lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD
-        if not render:
+        if offset is not None:
+            raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned map cannot be '
+                             'corrected afterwards (use frame="world", or pull_point_cloud)')
+        if not render:   # every camera, before anything is allocated or launched
             for c in cams:
-                if c not in self._depth_valid:
-                    raise _lib.SmjError(f"render=False: {c.name} has not been rendered yet (pull_camera_data() or pull_point_cloud() first)")
-        key = (frame, (ny, nx))
-        bufs = self._hmaps.get(key)
-        if bufs is None:
-            bufs = self._hmaps[key] = (torch.full((self.num_envs, ny, nx), float("nan"), dtype=torch.float32, device=self.device),
-                                       torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device))
+                self._depth_image(c, False)
+        bufs = self._cached(self._hmaps, (frame, (ny, nx)), lambda: (
+            torch.full((self.num_envs, ny, nx), float("nan"), dtype=torch.float32, device=self.device),
+            torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device)))
         for k, c in enumerate(cams):
-            st = c.initial_camera_settings
-            img = self._depth[c]
-            if render:
-                self._render_depth_into(c, img)
-                self._depth_valid.add(c)
-            rc = self._L.smj_depth_to_heightmap(self._ctx, self.names["camera"].index(c.camera_name_in_mjcf), st.width, st.height,
-                                                float(st.field_of_view_vertical_in_degrees), ctypes.c_void_p(img.data_ptr()), stride, fr,
+            img = self._depth_image(c, render)
+            rc = self._L.smj_depth_to_heightmap(self._ctx, *self._camera_args(c), ctypes.c_void_p(img.data_ptr()), stride, fr,
                                                 x0, y0, cell, nx, ny, lo, hi, int(k > 0), ctypes.c_void_p(bufs[0].data_ptr()),
                                                 ctypes.c_void_p(bufs[1].data_ptr()), self._stream())
             _lib.check(self._L, self._ctx, rc, "smj_depth_to_heightmap")
-        return StatusStretchHeightMap(time=self.nstep.to(torch.float64) * self.timestep, height=bufs[0], count=bufs[1], origin=(x0, y0),
+        return StatusStretchHeightMap(time=self._time(), height=bufs[0], count=bufs[1], origin=(x0, y0),
                                       cell=cell, frame=frame)
 
     @_require_connection
@@ -469,44 +475,23 @@ class StretchBatchSimulator:
         The tensors are simulator-owned and overwritten (or added to) by the next call with the same (frame, shape)."""
         if not self._read_flags & _lib.READ_LIDAR:
             raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
-        if frame not in ("world", "base"):
-            raise ValueError('frame must be "world" or "base"')
-        try:
-            ny, nx = (int(v) for v in shape)
-            x0, y0 = (float(v) for v in origin)
-            r_min, r_max = (float(v) for v in range_limits)
-        except (TypeError, ValueError):
-            raise ValueError("shape = (ny, nx), origin = (x0, y0), range_limits = (r_min, r_max)") from None
-        if ny < 1 or nx < 1 or ny * nx > 65536:
-            raise ValueError("shape: ny, nx >= 1 and ny * nx <= 65536")
-        cell = float(cell)
-        if not (np.isfinite(cell) and cell > 0):
-            raise ValueError("cell must be finite and > 0")
-        if not (np.isfinite(x0) and np.isfinite(y0)):
-            raise ValueError("origin must be finite")
+        fr, offset = self._frame_id(frame, ("world", "base"))
+        ny, nx, x0, y0, cell, r_min, r_max = self._grid_args(shape, origin, cell, range_limits, "range_limits = (r_min, r_max)")
         if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
             raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
         if np.float32(r_max) / np.float32(cell) > 8192:
             raise ValueError("range_limits[1] / cell must not exceed 8192")
-        if frame == "base":
-            i = self.names["body"].index("base_link")
-            fr = int(self.model["link_fused"][i])
-            if np.any(np.asarray(self.model["link_relpos"][i], np.float64) != 0) or not torch.equal(
-                    self._quat_mat(self.model["link_relquat"][i], self.device), torch.eye(3, device=self.device)):
-                raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned grid cannot be '
-                                 'corrected afterwards (use frame="world")')
-        else:
-            fr = _lib.FRAME_WORLD
-        key = (frame, (ny, nx))
-        bufs = self._occ.get(key)
-        if bufs is None:
-            bufs = self._occ[key] = (torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device),
-                                     torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device))
+        if offset is not None:
+            raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned grid cannot be '
+                             'corrected afterwards (use frame="world")')
+        bufs = self._cached(self._occ, (frame, (ny, nx)), lambda: (
+            torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device),
+            torch.zeros(self.num_envs, ny, nx, dtype=torch.int32, device=self.device)))
         rc = self._L.smj_lidar_to_occupancy(self._ctx, ctypes.c_void_p(self.lidar.data_ptr()), self.num_envs, fr, x0, y0, cell, nx, ny,
                                             r_min, r_max, int(bool(no_return_clears)), int(bool(accumulate)),
                                             ctypes.c_void_p(bufs[0].data_ptr()), ctypes.c_void_p(bufs[1].data_ptr()), self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_lidar_to_occupancy")
-        return StatusStretchOccupancyGrid(time=self.nstep.to(torch.float64) * self.timestep, hit=bufs[0], miss=bufs[1], origin=(x0, y0),
+        return StatusStretchOccupancyGrid(time=self._time(), hit=bufs[0], miss=bufs[1], origin=(x0, y0),
                                           cell=cell, frame=frame)
 
     @_require_connection
@@ -572,9 +557,7 @@ class StretchBatchSimulator:
             if not (np.isfinite(max_distance) and max_distance > 0):
                 raise ValueError("max_distance: metres, finite and > 0 (None = no bound)")
             R = int(min(math.ceil(max_distance / cell), 8192))   # beyond the longest diagonal every bound is none
-        bufs = self._dist.get((ny, nx))
-        if bufs is None:
-            bufs = self._dist[(ny, nx)] = [torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device), None]
+        bufs = self._cached(self._dist, (ny, nx), lambda: [torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device), None])
         if nearest and bufs[1] is None:
             bufs[1] = torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device)
         near = bufs[1] if nearest else None
@@ -582,7 +565,7 @@ class StretchBatchSimulator:
                                                nx, ny, min_hits, int(bool(unknown_is_obstacle)), R, ctypes.c_void_p(bufs[0].data_ptr()),
                                                ctypes.c_void_p(near.data_ptr()) if near is not None else None, self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_distance")
-        return StatusStretchDistanceField(time=self.nstep.to(torch.float64) * self.timestep, dist2=bufs[0], nearest=near, origin=x0y0, cell=cell,
+        return StatusStretchDistanceField(time=self._time(), dist2=bufs[0], nearest=near, origin=x0y0, cell=cell,
                                           frame=frame)
 
     @_require_connection
@@ -592,7 +575,7 @@ class StretchBatchSimulator:
         if not self._contacts:
             raise _lib.SmjError("the contact readout is off: construct StretchBatchSimulator(..., contacts=True)")
         return StatusStretchContacts.from_records(self.contact_records, self.info[1], self._geom_body,
-                                                  time=self.nstep.to(torch.float64) * self.timestep)
+                                                  time=self._time())
 
     def _body_ids(self, bodies) -> torch.Tensor:
         """MJCF body name(s) -> their ids as a device tensor, cached per name set: a per-step query copies nothing to the device (a

@@ -5,19 +5,12 @@
 // over all obstacle cells with the key (dist2, index), on seeded grids and on grids full of ties, with and without R.  Every cell
 // must be written exactly once.  Prints "ok" at the end.
 #include "smj_edt.h"
+#include "host_check.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
-
-static int failures = 0;
-#define CHECK(cond, ...)                                \
-  do {                                                  \
-    if (!(cond)) {                                      \
-      if (failures++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } \
-    }                                                   \
-  } while (0)
 
 struct Field { std::vector<int> dist2, nearest; };
 

@@ -1,9 +1,10 @@
 // Host harness of the height-map arithmetic (stretch_mujoco_amd/csrc/smj_hmap.h): the inline functions the HIP kernel calls,
 // compiled for the host.  The order-preserving key (strictly monotone, round trip, key 0 never produced), the cell rule at and
-// around boundaries and on values no int can hold, the cut into bands, and a serial emulation of the kernel's scatter on a seeded
+// around boundaries and on values no int can hold, the cut into bands, the split of a band store, and a serial emulation of the kernel's scatter on a seeded
 // image against long-hand fp64 by the comparison rule of tests/height_map_ref.py -- the same grid as one band and as several gives
 // identical arrays.  Prints "ok" at the end.
 #include "smj_hmap.h"
+#include "host_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -13,18 +14,6 @@
 #include <limits>
 #include <random>
 #include <vector>
-
-static int failures = 0;
-#define CHECK(cond, ...)                                \
-  do {                                                  \
-    if (!(cond)) {                                      \
-      if (failures++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } \
-    }                                                   \
-  } while (0)
-
-static float from_bits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
-static uint32_t to_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
-static const float INF = std::numeric_limits<float>::infinity();
 
 static void check_key() {
   std::vector<float> v = {0.f, -0.f, from_bits(1u), from_bits(0x007fffffu), from_bits(0x00800000u), from_bits(0x7f7fffffu),
@@ -60,7 +49,6 @@ static bool cell_of(float x, float y, float z, float x0, float y0, float cell, i
 
 static void check_cell_rule() {
   int ix, iy;
-  const float NaN = std::numeric_limits<float>::quiet_NaN();
   // a grid whose edges are exact in fp32: origin -2, cell 0.25 (inv_cell 4), 16 x 8
   const float x0 = -2.f, y0 = -1.f, c = 0.25f;
   const int nx = 16, ny = 8;
@@ -131,6 +119,33 @@ static void check_bands() {
   CHECK(smj_hmap_bands(128, 128, SMJ_HMAP_BAND_CELLS) == 4 && smj_hmap_bands(64, 96, SMJ_HMAP_BAND_CELLS) == 2, "128 x 128 is four bands, 64 x 96 two");
 }
 
+// the split of a band store against a brute-force enumeration: every cell stored exactly once, the groups on 16-byte boundaries
+static void check_store_split() {
+  for (int ncell = 0; ncell <= 40; ncell++)
+    for (int mis = 0; mis <= 3; mis++) {
+      const uintptr_t out = 0x1000u + 4u * (unsigned)mis;
+      const smj_hmap_split_t s = smj_hmap_store_split(out, ncell);
+      std::vector<int> stored((size_t)ncell, 0);
+      bool inside = true;
+      for (int g = 0; g < s.groups; g++) {
+        const int c = s.lead + 4 * g;
+        CHECK((out + 4u * (unsigned)c) % 16u == 0, "ncell %d misaligned by %d words: group %d starts off a 16-byte boundary", ncell, mis, g);
+        for (int k = 0; k < 4; k++) {
+          if (c + k >= 0 && c + k < ncell) stored[(size_t)(c + k)]++;
+          else inside = false;
+        }
+      }
+      for (int t = 0; t < s.rest; t++) {
+        const int c = smj_hmap_split_rest(s, t);
+        if (c >= 0 && c < ncell) stored[(size_t)c]++;
+        else inside = false;
+      }
+      CHECK(inside, "ncell %d misaligned by %d words: a store outside the band", ncell, mis);
+      CHECK(s.lead >= 0 && s.lead <= 3 && s.rest >= 0 && s.rest <= 6, "ncell %d misaligned by %d words: lead %d rest %d", ncell, mis, s.lead, s.rest);
+      for (int c = 0; c < ncell; c++) CHECK(stored[(size_t)c] == 1, "ncell %d misaligned by %d words: cell %d stored %d times", ncell, mis, c, stored[(size_t)c]);
+    }
+}
+
 struct Map { std::vector<float> z; std::vector<int> n; };
 
 // what one launch does, serially: per band the two arrays, every kept pixel scattered with max / add, decoded and stored once
@@ -167,8 +182,6 @@ static void emulate(const std::vector<float>& depth, int W, int H, int stride, f
 static bool same(const Map& a, const Map& b) {
   return a.z.size() == b.z.size() && !memcmp(a.z.data(), b.z.data(), 4 * a.z.size()) && !memcmp(a.n.data(), b.n.data(), 4 * a.n.size());
 }
-
-struct Pose { float p[3], m[9]; };
 
 static void check_scatter(int W, int H, int stride, int nx, int ny, float cell, float x0, float y0, float zl, float zh, unsigned seed) {
   // camera 1.3 m up, pitched 0.75 rad down and yawed 0.45 (the scene of tests/height_map_ref.py), as body pose + camera offset
@@ -299,6 +312,7 @@ int main() {
   check_key();
   check_cell_rule();
   check_bands();
+  check_store_split();
   check_scatter(37, 23, 1, 64, 64, 0.05f, -1.613f, -1.587f, -0.05f, 1.0f, 1);
   check_scatter(424, 240, 1, 64, 64, 0.05f, -1.613f, -1.587f, -0.05f, 1.0f, 2);
   check_scatter(424, 240, 3, 16, 12, 0.05f, 0.487f, -0.313f, -0.05f, 1.0f, 3);

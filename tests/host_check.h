@@ -1,0 +1,39 @@
+// What the host check programs of the device headers share (tests/{points,hmap,occ,edt}/*_check.cpp): the CHECK macro with its
+// failure counter, the special floats and bit casts, and a pose of fp32 numbers with a seeded random one.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <random>
+
+static int failures = 0;
+#define CHECK(cond, ...)                                \
+  do {                                                  \
+    if (!(cond)) {                                      \
+      if (failures++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } \
+    }                                                   \
+  } while (0)
+
+static inline float from_bits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
+static inline uint32_t to_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
+static const float INF = std::numeric_limits<float>::infinity();
+static const float NaN = std::numeric_limits<float>::quiet_NaN();
+
+struct Pose { float p[3], m[9]; };
+
+static inline Pose random_pose(std::mt19937& g, double reach) {
+  std::normal_distribution<double> n(0, 1);
+  std::uniform_real_distribution<double> t(-reach, reach);
+  double q[4], s = 0;
+  for (double& x : q) { x = n(g); s += x * x; }
+  for (double& x : q) x /= std::sqrt(s);
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                       2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+  Pose P;
+  for (int k = 0; k < 9; k++) P.m[k] = (float)R[k];
+  for (int k = 0; k < 3; k++) P.p[k] = (float)t(g);
+  return P;
+}

@@ -4,6 +4,7 @@
 // long-hand fp64 by the comparison rule of tests/occupancy_ref.py -- the same grid as one band and as several gives identical
 // arrays, accumulate adds.  Prints "ok" at the end.
 #include "smj_occ.h"
+#include "host_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -15,17 +16,6 @@
 #include <set>
 #include <utility>
 #include <vector>
-
-static int failures = 0;
-#define CHECK(cond, ...)                                \
-  do {                                                  \
-    if (!(cond)) {                                      \
-      if (failures++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } \
-    }                                                   \
-  } while (0)
-
-static const float INF = std::numeric_limits<float>::infinity();
-static const float NaN = std::numeric_limits<float>::quiet_NaN();
 
 static void check_classify() {
   float len = -7.f;
@@ -144,7 +134,6 @@ static void check_guards() {
 }
 
 struct Grid { std::vector<int> hit, miss; };
-struct Pose { float p[3], m[9]; };
 struct Scan {
   Pose body, frame;
   std::vector<float> site_pos, lz, r;   // [K][3], [K][3], [K]

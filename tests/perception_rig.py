@@ -1,0 +1,82 @@
+"""The scene the GPU tests of the perception entries share (tests/test_gpu_{point_cloud,height_map,occupancy,distance}.py):
+stretch_scene, three envs driven apart, 200 steps.  Each test module keeps its own module-scoped fixture, which calls build() with
+its cameras and sensors and adds what only it needs."""
+import ctypes
+
+import numpy as np
+import torch
+
+B = 3
+# per env: base x, y, yaw; lift; wrist pitch (down: the wrist camera sees the floor inside its 1 m limit); head pan
+POSES = [(0.0, 0.0, 0.0, 0.6, -0.8, 0.0), (-0.3, 0.2, 0.5, 0.3, -0.6, -0.8), (-0.5, -0.3, -0.7, 0.45, -0.7, 0.6)]
+
+
+def f32(v):
+    return float(np.float32(v))
+
+
+def to32(v):
+    """fp64 of the fp32 value: the library rounds the model tables to fp32."""
+    return np.asarray(v, np.float64).astype(np.float32).astype(np.float64)
+
+
+class Rig:
+    pass
+
+
+def build(cameras=(), sensors=(), pose_arm_and_head=False):
+    """The started simulator after 200 steps, with the host copies every module reads.  pose_arm_and_head: the arm, the wrist pitch
+    and the head pan are set per env too (what the cameras look at); without it only the base pose and the lift differ."""
+    from stretch_mujoco_amd import StretchBatchSimulator, lib
+    from stretch_mujoco_amd.enums import StretchCameras
+
+    sim = StretchBatchSimulator(num_envs=B, device="cuda:0", cameras_to_use=list(cameras), sensors_to_use=list(sensors), solver="newton",
+                                scene="stretch_scene")
+    sim.start(home=False)
+    jn = {n: i for i, n in enumerate(sim.names["joint"])}
+    an = {n: i for i, n in enumerate(sim.names["actuator"])}
+    adr = sim.model["jnt_qposadr"]
+    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
+    ctrl = np.zeros((sim.nu, B))
+    for e, (x, y, yaw, lift, pitch, pan) in enumerate(POSES):
+        q[0:2, e] = [x, y]
+        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
+        q[adr[jn["joint_lift"]], e] = lift
+        ctrl[an["lift"], e] = lift
+        if pose_arm_and_head:
+            for k in range(4):
+                q[adr[jn[f"joint_arm_l{k}"]], e] = 0.025
+            q[adr[jn["joint_wrist_pitch"]], e] = pitch
+            q[adr[jn["joint_head_pan"]], e] = pan
+            ctrl[an["arm"], e], ctrl[an["wrist_pitch"], e], ctrl[an["head_pan"], e] = 0.1, pitch, pan
+    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
+    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
+    sim.step(200)
+    torch.cuda.synchronize()
+    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
+    r = Rig()
+    r.sim, r.L, r.lib, r.cams = sim, lib.load(), lib, StretchCameras
+    r.xpose = sim.xpose.cpu().numpy().astype(np.float64)
+    r.cam_names = sim.names["camera"]
+    r.cam_pos = to32(sim.model["cam_pos"])
+    r.cam_mat = to32(sim.model["k_cam_mat"])
+    r.cam_bodyid = np.asarray(sim.model["cam_bodyid"]).reshape(-1)
+    r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
+    r.cache = {}
+    return r
+
+
+def frame_id(r, frame):
+    """The C entries' frame id; the fused body of base_link goes by "body" in the camera tests and by "base" in the lidar tests."""
+    return {"camera": r.lib.FRAME_CAMERA, "world": r.lib.FRAME_WORLD, "body": r.base, "base": r.base}[frame]
+
+
+def render(r, ci, W, H, fovy, limit):
+    """(device image, host copy), rendered once per (camera, size, limit) and left unchanged."""
+    key = ("img", ci, W, H, fovy, limit)
+    if key not in r.cache:
+        img = torch.zeros(B, H, W, dtype=torch.float32, device=r.sim.device)
+        assert r.L.smj_render_depth(r.sim._ctx, ci, W, H, float(fovy), float(limit), ctypes.c_void_p(img.data_ptr()), r.sim._stream()) == 0
+        torch.cuda.synchronize()
+        r.cache[key] = (img, img.cpu().numpy())
+    return r.cache[key]

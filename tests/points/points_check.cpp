@@ -2,6 +2,7 @@
 // compiled for the host and checked against long-hand fp64 -- the index mapping (every grid cell of every env hit exactly once,
 // nothing out of range), the per-pixel point in the three frame kinds, the NaN rule.  Prints "ok" at the end.
 #include "smj_points.h"
+#include "host_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -10,14 +11,6 @@
 #include <limits>
 #include <random>
 #include <vector>
-
-static int failures = 0;
-#define CHECK(cond, ...)                                \
-  do {                                                  \
-    if (!(cond)) {                                      \
-      if (failures++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } \
-    }                                                   \
-  } while (0)
 
 static void check_mapping(int W, int H, int s, int num_envs) {
   const int wp = smj_points_grid(W, s), hp = smj_points_grid(H, s);
@@ -52,23 +45,6 @@ static void check_mapping(int W, int H, int s, int num_envs) {
       CHECK(env == e2 && i == i2 && j == j2, "group at %lld, point %d", p0, k);
     }
   }
-}
-
-struct Pose { float p[3], m[9]; };
-
-static Pose random_pose(std::mt19937& g, double reach) {
-  std::normal_distribution<double> n(0, 1);
-  std::uniform_real_distribution<double> t(-reach, reach);
-  double q[4], s = 0;
-  for (double& x : q) { x = n(g); s += x * x; }
-  for (double& x : q) x /= std::sqrt(s);
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
-                       2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
-  Pose P;
-  for (int k = 0; k < 9; k++) P.m[k] = (float)R[k];
-  for (int k = 0; k < 3; k++) P.p[k] = (float)t(g);
-  return P;
 }
 
 // long-hand fp64 of one point from the same fp32 inputs

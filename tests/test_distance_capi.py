@@ -1,50 +1,29 @@
 """include/smj_distance.h (the distance-field entry; smj_occupancy.h includes it, so smj.h does) and the loader agree, as
 tests/test_occupancy_capi.py checks for smj_occupancy.h."""
-import ctypes
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-from conftest import ROOT
+import capi_check
 from stretch_mujoco_amd import lib
 
-
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
-
-
-def _declared(text):
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(smj_[a-z_]+)\s*\(", text)))
+ENTRY = ("smj_distance.h", lib.DISTANCE_EXPORTS, "smj_occupancy_to_distance")
 
 
 def test_header_and_loader_agree():
-    assert _declared(_header("smj_distance.h")) == sorted(lib.DISTANCE_EXPORTS) == ["smj_occupancy_to_distance"]
-    groups = [lib.EXPORTS, lib.POINT_EXPORTS, lib.HEIGHTMAP_EXPORTS, lib.OCCUPANCY_EXPORTS, lib.DISTANCE_EXPORTS]
-    for i, a in enumerate(groups):      # disjoint export tuples
-        for b in groups[i + 1:]:
-            assert not set(a) & set(b), (a, b)
-    others = [n for n in sorted(os.listdir(os.path.join(ROOT, "include"))) if n != "smj_distance.h"]
-    assert "smj_occupancy_to_distance" not in sum((_declared(_header(n)) for n in others), [])
-    assert int(re.search(r"#define\s+SMJ_DIST_NONE\s+\(1 << (\d+)\)", _header("smj_distance.h")).group(1)) == 30 and lib.DIST_NONE == 1 << 30
+    capi_check.header_and_loader_agree(*ENTRY)
+    assert int(re.search(r"#define\s+SMJ_DIST_NONE\s+\(1 << (\d+)\)", capi_check.header("smj_distance.h")).group(1)) == 30 and lib.DIST_NONE == 1 << 30
 
 
 def test_smj_occupancy_h_includes_it_after_its_declarations():
-    lines = _header("smj_occupancy.h").splitlines()
+    lines = capi_check.header("smj_occupancy.h").splitlines()
     inc = [k for k, line in enumerate(lines) if line.startswith('#include "smj_distance.h"')]
     assert len(inc) == 1
     closing = max(k for k, line in enumerate(lines) if line.strip() == "}")      # the end of extern "C"
     assert closing < inc[0] and lines[inc[0] + 1:] == ["#endif"] and lines[inc[0] - 1] == "#endif"
-    assert not any("smj_distance.h" in line for line in _header("smj.h").splitlines() if line.startswith("#include"))
+    assert "smj_distance.h" not in capi_check.smj_h_includes()[1]
 
 
 def test_constants_of_the_kernel_header():
-    with open(os.path.join(ROOT, "stretch_mujoco_amd", "csrc", "smj_edt.h")) as f:
-        text = f.read()
+    text = capi_check.kernel_header("smj_edt.h")
     assert re.search(r"SMJ_EDT_NONE\s*=\s*1 << 30", text)
     assert int(re.search(r"SMJ_EDT_MAX_CELLS\s*=\s*(\d+)", text).group(1)) == 65536
     assert int(re.search(r"SMJ_EDT_MAX_SIDE\s*=\s*(\d+)", text).group(1)) == 4096
@@ -52,29 +31,12 @@ def test_constants_of_the_kernel_header():
 
 
 def test_library_exports_the_entry_with_its_signature():
-    if not os.path.exists(lib.LIB_PATH):
-        pytest.fail(f"{lib.LIB_PATH} not built: run __graft_entry__.build()")
-    L = lib.load()
-    for sym in lib.DISTANCE_EXPORTS:
-        assert hasattr(L, sym), sym
-    decl = re.search(r"int smj_occupancy_to_distance\((.*?)\);", _header("smj_distance.h"), flags=re.S).group(1)
-    args = [a.strip() for a in decl.split(",")]
-    assert len(args) == len(L.smj_occupancy_to_distance.argtypes) == 11
-    for a, t in zip(args, L.smj_occupancy_to_distance.argtypes):
-        want = ctypes.c_void_p if "*" in a else {"int": ctypes.c_int}[a.split()[0]]
-        assert t is want, (a, t)
+    capi_check.library_exports(*ENTRY, 11)
 
 
 def test_c_caller_compiles_against_smj_h_alone(tmp_path):
     """A C99 translation unit that includes only smj.h sees the entry and SMJ_DIST_NONE; so does one that includes smj_distance.h or
     smj_occupancy.h first."""
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler on this box")
     body = ("int f(smj_ctx* c, const void* h, const void* m, void* d, void* n) { return smj_occupancy_to_distance(c, h, m, 128, 128, 1, 0, 20, d, n, 0) "
             "+ (SMJ_DIST_NONE == 1073741824 ? 0 : 1); }\n")
-    for first in ("smj.h", "smj_distance.h", "smj_occupancy.h"):
-        src = tmp_path / f"use_{first[:-2]}.c"
-        src.write_text(f'#include "{first}"\n' + body)
-        subprocess.check_call([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
-                               str(tmp_path / "use.o")])
+    capi_check.c_caller_compiles(tmp_path, body, ("smj.h", "smj_distance.h", "smj_occupancy.h"))

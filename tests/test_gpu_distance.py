@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import distance_ref as ref
+import perception_rig
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -271,37 +272,14 @@ def test_error_codes_and_a_refused_call_writes_nothing(bare):
 
 # ------------------------------------------------------------------ the simulator
 
-class Rig:
-    pass
-
-
 @pytest.fixture(scope="module")
 def rig():
     """The rig of tests/test_gpu_occupancy.py: stretch_scene, three envs driven apart, 200 steps, the lidar on."""
-    from stretch_mujoco_amd import StretchBatchSimulator
     from stretch_mujoco_amd.enums import StretchSensors
 
-    sim = StretchBatchSimulator(num_envs=B, device=DEV, sensors_to_use=[StretchSensors.base_lidar], solver="newton", scene="stretch_scene")
-    sim.start(home=False)
-    jn = {n: i for i, n in enumerate(sim.names["joint"])}
-    an = {n: i for i, n in enumerate(sim.names["actuator"])}
-    adr = sim.model["jnt_qposadr"]
-    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
-    ctrl = np.zeros((sim.nu, B))
-    for e, (x, y, yaw, lift) in enumerate([(0.0, 0.0, 0.0, 0.6), (-0.3, 0.2, 0.5, 0.3), (-0.5, -0.3, -0.7, 0.45)]):
-        q[0:2, e] = [x, y]
-        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
-        q[adr[jn["joint_lift"]], e] = lift
-        ctrl[an["lift"], e] = lift
-    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
-    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
-    sim.step(200)
-    torch.cuda.synchronize()
-    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
-    r = Rig()
-    r.sim = sim
+    r = perception_rig.build(sensors=[StretchSensors.base_lidar])
     yield r
-    sim.stop()
+    r.sim.stop()
 
 
 def test_end_to_end_from_the_lidar_scan(rig):

@@ -22,81 +22,32 @@ import pytest
 import torch
 
 import height_map_ref as ref
+import perception_rig
+from perception_rig import B, f32
+from perception_rig import frame_id as _fid
+from perception_rig import render as _render
 from point_cloud_ref import body_pose, camera_pose, deproject, pixel_dirs
 
 pytestmark = pytest.mark.gpu
 
-B = 3
 SMALL = (37, 23)
 X0, Y0 = -1.613, -1.587
 INF = float("inf")
 
 
-def f32(v):
-    return float(np.float32(v))
-
-
-class Rig:
-    pass
-
-
 @pytest.fixture(scope="module")
 def rig():
-    from stretch_mujoco_amd import StretchBatchSimulator, lib
     from stretch_mujoco_amd.enums import StretchCameras
 
-    cams = StretchCameras.depth() + [StretchCameras.cam_d405_rgb]
-    sim = StretchBatchSimulator(num_envs=B, device="cuda:0", cameras_to_use=cams, solver="newton", scene="stretch_scene")
-    sim.start(home=False)
-    jn = {n: i for i, n in enumerate(sim.names["joint"])}
-    an = {n: i for i, n in enumerate(sim.names["actuator"])}
-    adr = sim.model["jnt_qposadr"]
-    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
-    ctrl = np.zeros((sim.nu, B))
-    # per env: base x, y, yaw; lift; wrist pitch (down: the wrist camera sees the floor inside its 1 m limit); head pan
-    for e, (x, y, yaw, lift, pitch, pan) in enumerate([(0.0, 0.0, 0.0, 0.6, -0.8, 0.0), (-0.3, 0.2, 0.5, 0.3, -0.6, -0.8),
-                                                       (-0.5, -0.3, -0.7, 0.45, -0.7, 0.6)]):
-        q[0:2, e] = [x, y]
-        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
-        q[adr[jn["joint_lift"]], e] = lift
-        for k in range(4):
-            q[adr[jn[f"joint_arm_l{k}"]], e] = 0.025
-        q[adr[jn["joint_wrist_pitch"]], e] = pitch
-        q[adr[jn["joint_head_pan"]], e] = pan
-        ctrl[an["lift"], e], ctrl[an["arm"], e], ctrl[an["wrist_pitch"], e], ctrl[an["head_pan"], e] = lift, 0.1, pitch, pan
-    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
-    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
-    sim.step(200)
-    torch.cuda.synchronize()
-    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
-    r = Rig()
-    r.sim, r.L, r.lib, r.cams = sim, lib.load(), lib, StretchCameras
-    r.xpose = sim.xpose.cpu().numpy().astype(np.float64)
-    r.cam_names = sim.names["camera"]
-    r.cam_pos = np.asarray(sim.model["cam_pos"], np.float64).astype(np.float32).astype(np.float64)       # the library rounds them to fp32
-    r.cam_mat = np.asarray(sim.model["k_cam_mat"], np.float64).astype(np.float32).astype(np.float64)
-    r.cam_bodyid = np.asarray(sim.model["cam_bodyid"]).reshape(-1)
-    r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
-    r.cache = {}
+    r = perception_rig.build(cameras=StretchCameras.depth() + [StretchCameras.cam_d405_rgb], pose_arm_and_head=True)
     yield r
-    sim.stop()
+    r.sim.stop()
 
 
 def _cam(r, which):
     cam = r.cams[which]
     st = cam.initial_camera_settings
     return cam, st, r.cam_names.index(cam.camera_name_in_mjcf), float(st.field_of_view_vertical_in_degrees)
-
-
-def _render(r, ci, W, H, fovy, limit):
-    """(device image, host copy), rendered once per (camera, size, limit) and left unchanged."""
-    key = ("img", ci, W, H, fovy, limit)
-    if key not in r.cache:
-        img = torch.zeros(B, H, W, dtype=torch.float32, device=r.sim.device)
-        assert r.L.smj_render_depth(r.sim._ctx, ci, W, H, float(fovy), float(limit), ctypes.c_void_p(img.data_ptr()), r.sim._stream()) == 0
-        torch.cuda.synchronize()
-        r.cache[key] = (img, img.cpu().numpy())
-    return r.cache[key]
 
 
 def _hmap(r, ci, W, H, fovy, depth, stride, frame, x0, y0, cell, nx, ny, zl, zh, acc=0, out=None, count=True, ctx=None, rc=0):
@@ -142,10 +93,6 @@ def _compare(tag, height, count, bds):
         bad = ref.check_map(h[e], n[e], bd)
         assert not bad, (tag, e, len(bad), bad[:5])
     return h, n
-
-
-def _fid(r, frame):
-    return {"camera": r.lib.FRAME_CAMERA, "world": r.lib.FRAME_WORLD, "body": r.base}[frame]
 
 
 def _origin_around(pts, nx, ny, cell):

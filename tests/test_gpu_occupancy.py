@@ -18,60 +18,32 @@ import pytest
 import torch
 
 import occupancy_ref as ref
+import perception_rig
+from perception_rig import B, f32, to32
+from perception_rig import frame_id as _fid
 from point_cloud_ref import body_pose
 
 pytestmark = pytest.mark.gpu
 
-B = 3
 K = 360
 NaN = float("nan")
 INF = float("inf")
 LIMITS = (0.2, 9.5)
 
 
-def f32(v):
-    return float(np.float32(v))
-
-
-class Rig:
-    pass
-
-
 @pytest.fixture(scope="module")
 def rig():
-    from stretch_mujoco_amd import StretchBatchSimulator, lib
     from stretch_mujoco_amd.enums import StretchSensors
 
-    sim = StretchBatchSimulator(num_envs=B, device="cuda:0", sensors_to_use=[StretchSensors.base_lidar], solver="newton", scene="stretch_scene")
-    sim.start(home=False)
-    jn = {n: i for i, n in enumerate(sim.names["joint"])}
-    an = {n: i for i, n in enumerate(sim.names["actuator"])}
-    adr = sim.model["jnt_qposadr"]
-    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
-    ctrl = np.zeros((sim.nu, B))
-    for e, (x, y, yaw, lift) in enumerate([(0.0, 0.0, 0.0, 0.6), (-0.3, 0.2, 0.5, 0.3), (-0.5, -0.3, -0.7, 0.45)]):      # per env: base x, y, yaw; lift
-        q[0:2, e] = [x, y]
-        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
-        q[adr[jn["joint_lift"]], e] = lift
-        ctrl[an["lift"], e] = lift
-    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
-    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
-    sim.step(200)
-    torch.cuda.synchronize()
-    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
-    r = Rig()
-    r.sim, r.L, r.lib = sim, lib.load(), lib
+    r = perception_rig.build(sensors=[StretchSensors.base_lidar])
+    sim = r.sim
     assert sim.nlidar == K
     r.scan = sim.lidar[:K].clone()                      # [K, B] batch-major, ld = B: what SMJ_SLOT_LIDAR holds
     r.scan_host = r.scan.cpu().numpy()
-    r.xpose = sim.xpose.cpu().numpy().astype(np.float64)
-    to32 = lambda v: np.asarray(v, np.float64).astype(np.float32).astype(np.float64)      # the library rounds the tables to fp32
     sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
     r.site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
     r.site_pos = to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
     r.lz = to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
-    r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
-    r.cache = {}
     yield r
     sim.stop()
 
@@ -92,10 +64,6 @@ def _geometry(r, frame, xpose=None):
     if xpose is None:
         r.cache[key] = out
     return out
-
-
-def _fid(r, frame):
-    return {"world": r.lib.FRAME_WORLD, "base": r.base}[frame]
 
 
 def _new(r, nx, ny, fill=7):

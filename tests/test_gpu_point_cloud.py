@@ -15,57 +15,23 @@ import numpy as np
 import pytest
 import torch
 
+import perception_rig
+from perception_rig import B
 from point_cloud_ref import body_pose, camera_pose, deproject, pixel_dirs
 
 pytestmark = pytest.mark.gpu
 
-B = 3
 SMALL = (37, 23)
 STRIDES = (1, 2, 3, 5)
 EPS = 32 * 2.0 ** -24
 
 
-class Rig:
-    pass
-
-
 @pytest.fixture(scope="module")
 def rig():
-    from stretch_mujoco_amd import StretchBatchSimulator, lib
     from stretch_mujoco_amd.enums import StretchCameras
 
-    cams = StretchCameras.depth() + [StretchCameras.cam_d405_rgb]
-    sim = StretchBatchSimulator(num_envs=B, device="cuda:0", cameras_to_use=cams, solver="newton", scene="stretch_scene")
-    sim.start(home=False)
-    jn = {n: i for i, n in enumerate(sim.names["joint"])}
-    an = {n: i for i, n in enumerate(sim.names["actuator"])}
-    adr = sim.model["jnt_qposadr"]
-    q = np.stack([np.asarray(sim.model["qpos0"], np.float64)] * B, 1)
-    ctrl = np.zeros((sim.nu, B))
-    # per env: base x, y, yaw; lift; wrist pitch (down: the wrist camera sees the floor inside its 1 m limit); head pan
-    for e, (x, y, yaw, lift, pitch, pan) in enumerate([(0.0, 0.0, 0.0, 0.6, -0.8, 0.0), (-0.3, 0.2, 0.5, 0.3, -0.6, -0.8),
-                                                       (-0.5, -0.3, -0.7, 0.45, -0.7, 0.6)]):
-        q[0:2, e] = [x, y]
-        q[3:7, e] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
-        q[adr[jn["joint_lift"]], e] = lift
-        for k in range(4):
-            q[adr[jn[f"joint_arm_l{k}"]], e] = 0.025
-        q[adr[jn["joint_wrist_pitch"]], e] = pitch
-        q[adr[jn["joint_head_pan"]], e] = pan
-        ctrl[an["lift"], e], ctrl[an["arm"], e], ctrl[an["wrist_pitch"], e], ctrl[an["head_pan"], e] = lift, 0.1, pitch, pan
-    sim.qpos[:] = torch.tensor(q, dtype=torch.float32, device=sim.device)
-    sim.ctrl[:] = torch.tensor(ctrl, dtype=torch.float32, device=sim.device)
-    sim.step(200)
-    torch.cuda.synchronize()
-    assert int((sim.info[3] & 4).max()) == 0, "an env was reset for a non-finite state"
-    r = Rig()
-    r.sim, r.L, r.lib, r.cams = sim, lib.load(), lib, StretchCameras
-    r.xpose = sim.xpose.cpu().numpy().astype(np.float64)
-    r.cam_names = sim.names["camera"]
-    r.cam_pos = np.asarray(sim.model["cam_pos"], np.float64).astype(np.float32).astype(np.float64)       # the library rounds them to fp32
-    r.cam_mat = np.asarray(sim.model["k_cam_mat"], np.float64).astype(np.float32).astype(np.float64)
-    r.cam_bodyid = np.asarray(sim.model["cam_bodyid"]).reshape(-1)
-    r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
+    r = perception_rig.build(cameras=StretchCameras.depth() + [StretchCameras.cam_d405_rgb], pose_arm_and_head=True)
+    sim = r.sim
     # the three transforms differ
     for cam in StretchCameras.depth():
         cp, _, _ = camera_pose(r.xpose, r.cam_bodyid, r.cam_pos, r.cam_mat, r.cam_names.index(cam.camera_name_in_mjcf))
@@ -85,9 +51,7 @@ def _points(r, ci, W, H, fovy, depth, stride, frame, out=None):
 
 
 def _render(r, ci, W, H, fovy, limit):
-    img = torch.zeros(B, H, W, dtype=torch.float32, device=r.sim.device)
-    assert r.L.smj_render_depth(r.sim._ctx, ci, W, H, float(fovy), float(limit), ctypes.c_void_p(img.data_ptr()), r.sim._stream()) == 0
-    return img
+    return perception_rig.render(r, ci, W, H, fovy, limit)[0]
 
 
 def _scale(r, ci, W, H, fovy, stride, depth, frame):

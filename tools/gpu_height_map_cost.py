@@ -10,9 +10,6 @@ Usage: python tools/gpu_height_map_cost.py [--envs 4096] [--rounds 5] [--reps 5]
 import argparse
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -22,42 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from stretch_mujoco_amd import StretchBatchSimulator  # noqa: E402
 from stretch_mujoco_amd.enums import StretchCameras  # noqa: E402
+from cost_common import LINES, resource_usage, say, timed  # noqa: E402
 
 BAND_CELLS = 4096      # SMJ_HMAP_BAND_CELLS of csrc/smj_hmap.h
-LINES = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def resource_usage():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    csrc = os.path.join(ROOT, "stretch_mujoco_amd", "csrc")
-    if not os.path.exists(hipcc):
-        say("kernel resource usage: no hipcc here")
-        return
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    p = subprocess.run([hipcc, *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "smj_hmap.hip", "-o", os.devnull], cwd=csrc,
-                       capture_output=True, text=True)
-    say("kernel resource usage (hipcc -Rpass-analysis=kernel-resource-usage, the Makefile's flags):")
-    for ln in p.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name: .*|VGPRs: .*|AGPRs: .*|TotalSGPRs: .*|ScratchSize.*|Occupancy.*|LDS Size.*|VGPRs Spill.*) \[-Rpass", ln)
-        if m:
-            t = m.group(1)
-            say(("  " if t.startswith("Function") else "    ") + t)
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():
@@ -70,7 +34,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("no GPU: nothing is measured")
     B = a.envs
-    resource_usage()
+    resource_usage("smj_hmap.hip")
     cams = StretchCameras.depth()
     sim = StretchBatchSimulator(num_envs=B, device="cuda:0", scene="stretch_scene", solver="newton", cameras_to_use=cams)
     sim.start(home=False)

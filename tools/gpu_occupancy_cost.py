@@ -11,9 +11,6 @@ Usage: python tools/gpu_occupancy_cost.py [--envs 4096] [--rounds 5] [--reps 5] 
 import argparse
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -22,58 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from stretch_mujoco_amd import StretchBatchSimulator, StretchSensors  # noqa: E402
-
-LINES = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def resource_usage():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    csrc = os.path.join(ROOT, "stretch_mujoco_amd", "csrc")
-    if not os.path.exists(hipcc):
-        say("kernel resource usage: no hipcc here")
-        return
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    p = subprocess.run([hipcc, *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "smj_occ.hip", "-o", os.devnull], cwd=csrc,
-                       capture_output=True, text=True)
-    say("kernel resource usage (hipcc -Rpass-analysis=kernel-resource-usage, the Makefile's flags):")
-    for ln in p.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name: .*|VGPRs: .*|AGPRs: .*|TotalSGPRs: .*|ScratchSize.*|Occupancy.*|LDS Size.*|VGPRs Spill.*) \[-Rpass", ln)
-        if m:
-            t = m.group(1)
-            say(("  " if t.startswith("Function") else "    ") + t)
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def alternate(fns, rounds, reps):
-    for f in fns.values():      # warm-up of every shape
-        f(); f()
-    torch.cuda.synchronize()
-    res = {k: [] for k in fns}
-    order = list(fns)
-    for r in range(rounds):
-        k0 = r % len(order)
-        for k in order[k0:] + order[:k0]:
-            res[k].append(timed(fns[k], reps))
-    return res, {k: float(np.median(v)) for k, v in res.items()}
-
-
-def fmt(res, med):
-    return "  ".join(f"{k} {med[k]:8.4f} [{min(res[k]):.4f} .. {max(res[k]):.4f}]" for k in res)
+from cost_common import LINES, alternate, fmt, resource_usage, say  # noqa: E402
 
 
 def main():
@@ -86,7 +32,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("no GPU: nothing is measured")
     B, dev = a.envs, "cuda:0"
-    resource_usage()
+    resource_usage("smj_occ.hip")
     sims = {}
     for name, sensors in (("lidar", [StretchSensors.base_lidar]), ("none", [])):
         sim = StretchBatchSimulator(num_envs=B, device=dev, scene="stretch_scene", solver="newton", sensors_to_use=sensors)

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from stretch_mujoco_amd import StretchBatchSimulator  # noqa: E402
 from stretch_mujoco_amd.enums import StretchCameras  # noqa: E402
+from cost_common import timed  # noqa: E402
 
 
 def torch_points(depth, W, H, fovy, stride, cpos, cmat):
@@ -32,16 +33,6 @@ def torch_points(depth, W, H, fovy, stride, cpos, cmat):
     pts = torch.einsum("bij,bhwj->bhwi", cmat, pc) + cpos[:, None, None, :]
     valid = torch.isfinite(d) & (d > 0)
     return torch.where(valid[..., None], pts, torch.full_like(pts, float("nan")))
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():

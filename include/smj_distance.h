@@ -46,4 +46,5 @@ int smj_occupancy_to_distance(smj_ctx* ctx, const void* hit_dev, const void* mis
 #ifdef __cplusplus
 }
 #endif
+#include "smj_navigation.h"
 #endif

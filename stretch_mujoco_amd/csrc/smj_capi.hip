@@ -26,6 +26,7 @@
 #include "smj_hmap.h"
 #include "smj_occ.h"
 #include "smj_edt.h"
+#include "smj_nav.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -820,6 +821,34 @@ int smj_occupancy_to_distance(smj_ctx* c, const void* hit_dev, const void* miss_
   const int R = max_dist_cells >= 2 * SMJ_EDT_MAX_SIDE ? 0 : max_dist_cells;
   smj_launch_edt(c->num_envs, (const int*)hit_dev, (const int*)miss_dev, nx, ny, min_hits, unknown_is_obstacle != 0, R, (int*)dist2_dev,
                  (int*)nearest_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_costmap_to_navigation(smj_ctx* c, const void* cost_dev, const void* goal_dev, int num_goals, int nx, int ny, int lethal, int neutral,
+                              void* potential_dev, void* next_dev, void* stream) {
+  if (!c) return -1;
+  if (!goal_dev || !potential_dev) return fail(c, -1, "null goal / potential buffer");
+  TRY(check_aligned(c, {goal_dev, potential_dev, next_dev}, "goal / potential / next buffer"));
+  if (nx < 1 || ny < 1 || nx > SMJ_NAV_MAX_SIDE || ny > SMJ_NAV_MAX_SIDE || (long long)nx * ny > SMJ_NAV_MAX_CELLS)
+    return fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, (int)SMJ_NAV_MAX_SIDE, (int)SMJ_NAV_MAX_CELLS);
+  if (num_goals < 1 || num_goals > SMJ_NAV_MAX_GOALS) return fail(c, -1, "num_goals %d outside [1, %d]", num_goals, (int)SMJ_NAV_MAX_GOALS);
+  if (lethal < 1 || lethal > 256) return fail(c, -1, "lethal %d outside [1, 256]: below 1 no cell is passable, above 256 means 256", lethal);
+  if (neutral < 1 || neutral > 255) return fail(c, -1, "neutral %d outside [1, 255]: a free step must cost something, and the potential must stay below 2^30", neutral);
+  // the workgroup of an env reads its inputs while it stores (the potential of a large grid is relaxed in place): no output may
+  // share a byte with an input or the other output
+  const uintptr_t cells = (uintptr_t)c->num_envs * (uintptr_t)nx * (uintptr_t)ny;
+  const uintptr_t in[2] = {(uintptr_t)cost_dev, (uintptr_t)goal_dev}, in_bytes[2] = {cells, (uintptr_t)c->num_envs * (uintptr_t)num_goals * 4u};
+  const uintptr_t out[2] = {(uintptr_t)potential_dev, (uintptr_t)next_dev}, bytes = cells * 4u;
+  for (int o = 0; o < 2; o++) {
+    if (!out[o]) continue;
+    for (int i = 0; i < 2; i++)
+      if (in[i] && out[o] < in[i] + in_bytes[i] && in[i] < out[o] + bytes) return fail(c, -1, "an output range overlaps an input range");
+  }
+  if (out[1] && out[0] < out[1] + bytes && out[1] < out[0] + bytes) return fail(c, -1, "the potential and next ranges overlap");
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_nav(c->num_envs, (const uint8_t*)cost_dev, (const int*)goal_dev, num_goals, nx, ny, lethal, neutral, (int*)potential_dev,
+                 (int*)next_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -222,6 +222,108 @@ class StatusStretchDistanceField:
         return cost.to(torch.uint8)
 
 
+def cells_of_points(points, origin, cell, ny, nx):
+    """int32 linear cell indices iy nx + ix of points [..., 2] (metres, x then y) in a grid laid out as StatusStretchOccupancyGrid's:
+    floor((p - origin) / cell); -1 for a point outside the grid or not finite.  On the points' device, no host synchronisation."""
+    import torch
+
+    p = points.to(torch.float32)
+    o = torch.tensor([float(origin[0]), float(origin[1])], dtype=torch.float32, device=p.device)
+    ij = torch.floor((p - o) / float(cell))
+    inside = torch.isfinite(ij).all(-1) & (ij[..., 0] >= 0) & (ij[..., 0] < nx) & (ij[..., 1] >= 0) & (ij[..., 1] < ny)
+    ij = torch.where(inside.unsqueeze(-1), ij, torch.zeros_like(ij)).to(torch.int32)
+    return torch.where(inside, ij[..., 1] * nx + ij[..., 0], torch.full_like(ij[..., 0], -1))
+
+
+@dataclass
+class StatusStretchNavigationField:
+    """New, without a reference counterpart: the exact cost-to-goal field of pull_navigation_field() (smj_costmap_to_navigation) over
+    a grid laid out as StatusStretchOccupancyGrid's.  `potential` and `next` are exact integers; the helpers turn them into metres,
+    offsets, headings and paths in torch.  Device tensors, simulator-owned, not synchronised to the host."""
+    time: Any
+    potential: Any      # [B, ny, nx] int32: cheapest path cost to a goal (axial move 5 (w(a) + w(b)), diagonal 7 (w(a) + w(b)), w = neutral + cost), 0 on a goal, NONE where there is no path
+    next: Any           # [B, ny, nx] int32 or None: linear index iy nx + ix of the neighbour to step to (the smallest among equally good ones), the cell itself on a goal, -1 where none
+    goal: Any           # [B, G] int32: the goal cells used, as linear indices; -1 = unused
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "base" or "world" ("grid" for a bare cost tensor)
+    neutral: int        # the weight of a zero-cost cell
+
+    NONE = 1 << 30      # SMJ_NAV_NONE
+
+    def distance(self):
+        """fp32 [B, ny, nx]: potential cell / (10 neutral) -- on a zero-cost map the octile path length to the goal in metres; inf
+        where there is no path."""
+        import torch
+
+        d = self.potential.to(torch.float32) * (float(self.cell) / (10.0 * float(self.neutral)))
+        return torch.where(self.potential >= self.NONE, torch.tensor(float("inf"), dtype=torch.float32, device=d.device), d)
+
+    def next_offset(self):
+        """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell to the neighbour to step to, zeros on goals and where there is no
+        path.  Needs pull_navigation_field(next=True)."""
+        import torch
+
+        if self.next is None:
+            raise ValueError("next_offset() needs pull_navigation_field(next=True)")
+        ny, nx = self.next.shape[-2:]
+        iy = torch.arange(ny, dtype=torch.int32, device=self.next.device).view(1, ny, 1)
+        ix = torch.arange(nx, dtype=torch.int32, device=self.next.device).view(1, 1, nx)
+        have = self.next >= 0
+        n = torch.where(have, self.next, 0)
+        dy = torch.where(have, torch.div(n, nx, rounding_mode="floor") - iy, 0)
+        dx = torch.where(have, n % nx - ix, 0)
+        return torch.stack((dy, dx), -1).to(torch.int32)
+
+    def heading(self):
+        """fp32 [B, ny, nx]: atan2(dy, dx) of next_offset(), the direction to drive in the grid's frame; NaN on goals and where there
+        is no path."""
+        import torch
+
+        off = self.next_offset().to(torch.float32)
+        h = torch.atan2(off[..., 0], off[..., 1])
+        still = (off[..., 0] == 0) & (off[..., 1] == 0)
+        return torch.where(still, torch.tensor(float("nan"), dtype=torch.float32, device=h.device), h)
+
+    def path(self, start, max_steps: int):
+        """int64 [B, max_steps + 1]: the cells visited from `start` along next, the start first; once the goal is reached the path
+        stays on it.  start, one per env: (x, y) in metres, a tensor [B, 2] in metres, or an int tensor [B] of cell indices.  -1
+        throughout for a start outside the grid or without a path.  Needs pull_navigation_field(next=True)."""
+        import torch
+
+        if self.next is None:
+            raise ValueError("path() needs pull_navigation_field(next=True)")
+        max_steps = int(max_steps)
+        if max_steps < 0:
+            raise ValueError("max_steps must be >= 0")
+        B, ny, nx = self.next.shape
+        dev = self.next.device
+        if not isinstance(start, torch.Tensor):
+            try:
+                x, y = (float(v) for v in start)
+            except (TypeError, ValueError):
+                raise ValueError("start: (x, y) in metres, a tensor [B, 2], or an int tensor [B] of cell indices") from None
+            start = torch.tensor([[x, y]], dtype=torch.float32, device=dev).expand(B, 2)
+        start = start.to(dev)
+        if start.is_floating_point():
+            if tuple(start.shape) != (B, 2):
+                raise ValueError(f"start in metres: [B = {B}, 2]")
+            cur = cells_of_points(start, self.origin, self.cell, ny, nx).to(torch.int64)
+        else:
+            if tuple(start.shape) != (B,):
+                raise ValueError(f"start as cell indices: [B = {B}]")
+            cur = start.to(torch.int64)
+            cur = torch.where((cur >= 0) & (cur < ny * nx), cur, torch.full_like(cur, -1))
+        flat = self.next.reshape(B, ny * nx).to(torch.int64)
+        step = lambda c: torch.where(c >= 0, flat.gather(1, c.clamp(min=0).unsqueeze(1)).squeeze(1), c)
+        cur = torch.where(step(cur) >= 0, cur, torch.full_like(cur, -1))      # a start without a path
+        out = [cur]
+        for _ in range(max_steps):
+            cur = step(cur)
+            out.append(cur)
+        return torch.stack(out, 1)
+
+
 @dataclass
 class StatusStretchContacts:
     """New, without a reference counterpart (like `step` / `reset`): the contact list of every env's last physics step and its

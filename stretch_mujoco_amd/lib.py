@@ -25,8 +25,10 @@ POINT_EXPORTS = ("smj_depth_to_points",)   # include/smj_pointcloud.h (smj.h inc
 HEIGHTMAP_EXPORTS = ("smj_depth_to_heightmap",)   # include/smj_heightmap.h (smj.h includes it)
 OCCUPANCY_EXPORTS = ("smj_lidar_to_occupancy",)   # include/smj_occupancy.h (smj.h includes it)
 DISTANCE_EXPORTS = ("smj_occupancy_to_distance",)   # include/smj_distance.h (smj_occupancy.h includes it, so smj.h does)
+NAVIGATION_EXPORTS = ("smj_costmap_to_navigation",)   # include/smj_navigation.h (smj_distance.h includes it, so smj.h does)
 BUILD_EXPORTS = ("smj_last_build",)   # include/smj_build.h (a header of its own: smj.h does not include it)
 DIST_NONE = 1 << 30   # SMJ_DIST_NONE: dist2 of a cell with no obstacle in reach
+NAV_NONE = 1 << 30   # SMJ_NAV_NONE: potential of a cell from which no goal can be reached
 FRAME_CAMERA, FRAME_WORLD = -1, -2   # smj_depth_to_points: frame >= 0 is the frame of that fused body
 
 _lib = None
@@ -89,6 +91,7 @@ def load() -> ctypes.CDLL:
     L.smj_depth_to_heightmap.argtypes = [vp, ci, ci, ci, cf, vp, ci, ci, cf, cf, cf, ci, ci, cf, cf, ci, vp, vp, vp]
     L.smj_lidar_to_occupancy.argtypes = [vp, vp, cl, ci, cf, cf, cf, ci, ci, cf, cf, ci, ci, vp, vp, vp]
     L.smj_occupancy_to_distance.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+    L.smj_costmap_to_navigation.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
     L.smj_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_double]
     L.smj_base_controller_tick.argtypes = [vp, vp]
     L.smj_comm_init.argtypes = [vp, ci, ci, ctypes.c_char_p, ctypes.c_double]

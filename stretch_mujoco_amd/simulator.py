@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchHeightMap, StatusStretchJoints, StatusStretchOccupancyGrid, StatusStretchSensors
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -144,6 +144,7 @@ class StretchBatchSimulator:
         self._depth_valid = set()   # depth cameras whose image has been rendered (pull_point_cloud(render=False) needs one)
         self._hmaps = {}            # (frame, (ny, nx)) -> the simulator-owned (height, count) of pull_height_map
         self._occ = {}              # (frame, (ny, nx)) -> the simulator-owned (hit, miss) of pull_occupancy_grid
+        self._nav = {}              # (ny, nx, G) -> the simulator-owned [potential, next or None, goal] of pull_navigation_field
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
@@ -567,6 +568,111 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_distance")
         return StatusStretchDistanceField(time=self._time(), dist2=bufs[0], nearest=near, origin=x0y0, cell=cell,
                                           frame=frame)
+
+    @_require_connection
+    def pull_navigation_field(self, goal, cost=None, *, lethal: int = 253, neutral: int = 50, next: bool = False,
+                              inscribed_radius: float = 0.17, inflation_radius: float = 0.56, cost_scaling_factor: float = 10.0,
+                              cell=None, origin=None, **distance_kwargs) -> StatusStretchNavigationField:
+        """Exact cost-to-goal field (navigation function) of a costmap in one HIP pass (smj_costmap_to_navigation,
+        include/smj_navigation.h): per cell the cheapest path cost to a goal (`potential`) and, with next=True, the neighbour to
+        step to, the smallest linear index among equally good ones.  Integers only: two calls give identical tensors.  New, without
+        a reference counterpart; StatusStretchNavigationField turns it into metres, headings and paths.
+
+        goal, in metres in the grid's frame: (x, y) for every env, a tensor [B, 2], or [B, G, 2] with G <= 64; turned into cell
+        indices on the device (floor((g - origin) / cell); a goal outside the grid or not finite is unused).  An int tensor [B] or
+        [B, G] is taken as linear cell indices iy nx + ix directly (-1 = unused).  A goal on an impassable cell is skipped.
+        cost: None -- pull_distance_field(max_distance=inflation_radius, **distance_kwargs) is called and inflated by
+        .inflated_cost(inscribed_radius, inflation_radius, cost_scaling_factor); a StatusStretchDistanceField, inflated the same way,
+        whose frame, origin and cell are taken over; or a uint8 tensor [B, ny, nx] used as it is -- then cell and origin are these
+        keywords (1.0 and (0, 0) if absent) and the frame is "grid".
+        A cell is passable iff cost < lethal (1 .. 256; the default 253 keeps inscribed, lethal and unknown cells out, the
+        costmap convention) and weighs neutral + cost (neutral 1 .. 255).  An axial move between cells a, b costs
+        5 (w(a) + w(b)), a diagonal one 7 (w(a) + w(b)) and must not cut the corner of an impassable cell.
+        The tensors are simulator-owned and overwritten by the next call with the same (shape, G)."""
+        lethal, neutral = int(lethal), int(neutral)
+        if not 1 <= lethal <= 256:
+            raise ValueError("lethal must be in [1, 256]")
+        if not 1 <= neutral <= 255:
+            raise ValueError("neutral must be in [1, 255]")
+        B, dev = self.num_envs, self.device
+        # the goal's form, before anything runs; metres become cells once the grid is known
+        if isinstance(goal, torch.Tensor):
+            g = goal.to(dev)
+            if g.is_floating_point():
+                if g.dim() == 2:
+                    g = g.unsqueeze(1)
+                if g.dim() != 3 or g.shape[0] != B or g.shape[2] != 2 or not 1 <= g.shape[1] <= 64:
+                    raise ValueError(f"goal in metres: (x, y), a tensor [B = {B}, 2] or [B, G, 2] with 1 <= G <= 64")
+            elif g.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                if g.dim() == 1:
+                    g = g.unsqueeze(1)
+                if g.dim() != 2 or g.shape[0] != B or not 1 <= g.shape[1] <= 64:
+                    raise ValueError(f"goal as cell indices: an int tensor [B = {B}] or [B, G] with 1 <= G <= 64")
+            else:
+                raise ValueError("goal: a float tensor of metres or an int tensor of cell indices")
+        else:
+            try:
+                gx, gy = (float(v) for v in goal)
+            except (TypeError, ValueError):
+                raise ValueError(f"goal: (x, y) in metres, a tensor [B = {B}, 2] / [B, G, 2], or an int tensor [B] / [B, G]") from None
+            g = torch.tensor([[[gx, gy]]], dtype=torch.float32, device=dev).expand(B, 1, 2)
+        if cost is None or isinstance(cost, StatusStretchDistanceField):
+            r_ins, r_inf, k = float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor)
+            if not (0 <= r_ins <= r_inf < float("inf")) or not r_inf > 0 or not k >= 0:
+                raise ValueError("0 <= inscribed_radius <= inflation_radius, inflation_radius > 0, both finite; cost_scaling_factor >= 0")
+        if cost is None:
+            if "max_distance" in distance_kwargs:
+                raise ValueError("max_distance is the inflation_radius here")
+            if cell is not None:
+                distance_kwargs["cell"] = cell
+            if origin is not None:
+                distance_kwargs["origin"] = origin
+            cost = self.pull_distance_field(max_distance=r_inf, **distance_kwargs)
+            cell = origin = None
+        elif distance_kwargs:
+            raise ValueError(f"{sorted(distance_kwargs)}: keywords of pull_distance_field, which is called only for cost=None")
+        if isinstance(cost, StatusStretchDistanceField):
+            if cell is not None or origin is not None:
+                raise ValueError("cell and origin come from the StatusStretchDistanceField")
+            df = cost
+            frame, x0y0, cell = df.frame, tuple(df.origin), float(df.cell)
+            if df.dist2.dim() != 3 or df.dist2.shape[0] != B or df.dist2.device != dev:
+                raise ValueError(f"cost: a distance field [num_envs = {B}, ny, nx] on {dev}")
+            cost = df.inflated_cost(r_ins, r_inf, k)
+        else:
+            if not isinstance(cost, torch.Tensor) or cost.dtype != torch.uint8 or cost.dim() != 3 or cost.shape[0] != B:
+                raise ValueError(f"cost: None, a StatusStretchDistanceField, or a uint8 tensor [num_envs = {B}, ny, nx]")
+            try:
+                x0y0 = (0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
+                cell = 1.0 if cell is None else float(cell)
+            except (TypeError, ValueError):
+                raise ValueError("origin = (x0, y0), cell a number") from None
+            if len(x0y0) != 2 or not (np.isfinite(x0y0[0]) and np.isfinite(x0y0[1])):
+                raise ValueError("origin = (x0, y0), finite")
+            frame = "grid"
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        ny, nx = int(cost.shape[1]), int(cost.shape[2])
+        if ny < 1 or nx < 1 or ny > 4096 or nx > 4096 or ny * nx > 65536:
+            raise ValueError("cost: 1 <= ny, nx <= 4096 and ny * nx <= 65536")
+        cost = cost.to(device=dev).contiguous()
+        G = int(g.shape[1])
+        bufs = self._cached(self._nav, (ny, nx, G), lambda: [torch.empty(B, ny, nx, dtype=torch.int32, device=dev), None,
+                                                            torch.empty(B, G, dtype=torch.int32, device=dev)])
+        if next and bufs[1] is None:
+            bufs[1] = torch.empty(B, ny, nx, dtype=torch.int32, device=dev)
+        nxt = bufs[1] if next else None
+        if g.is_floating_point():
+            bufs[2].copy_(cells_of_points(g, x0y0, cell, ny, nx))
+        else:
+            g = g.to(torch.int64)
+            bufs[2].copy_(torch.where((g >= 0) & (g < ny * nx), g, torch.full_like(g, -1)))
+        rc = self._L.smj_costmap_to_navigation(self._ctx, ctypes.c_void_p(cost.data_ptr()), ctypes.c_void_p(bufs[2].data_ptr()), G, nx, ny,
+                                               lethal, neutral, ctypes.c_void_p(bufs[0].data_ptr()),
+                                               ctypes.c_void_p(nxt.data_ptr()) if nxt is not None else None, self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_costmap_to_navigation")
+        return StatusStretchNavigationField(time=self._time(), potential=bufs[0], next=nxt, goal=bufs[2], origin=x0y0, cell=cell,
+                                            frame=frame, neutral=neutral)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

@@ -1,5 +1,5 @@
 """What the cost tools of the perception entries share (gpu_point_cloud_cost.py, gpu_height_map_cost.py, gpu_occupancy_cost.py,
-gpu_distance_field_cost.py): the printed lines kept for the --out file, the compiler's resource report of a kernel source, device-event
+gpu_distance_field_cost.py, gpu_navigation_cost.py): the printed lines kept for the --out file, the compiler's resource report of a kernel source, device-event
 timing of back-to-back calls, and variants alternated round by round so that drift of the device affects them alike."""
 import os
 import re

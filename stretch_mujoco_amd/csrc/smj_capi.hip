@@ -169,6 +169,26 @@ static int check_grid(smj_ctx* c, int nx, int ny, int max_cells, float cell, flo
   return 0;
 }
 
+// a grid of integer cells (the distance and navigation entries: no cell size, no origin), within its kernel's limits
+static int check_cell_grid(smj_ctx* c, int nx, int ny, int max_side, int max_cells) {
+  return nx >= 1 && ny >= 1 && nx <= max_side && ny <= max_side && (long long)nx * ny <= max_cells
+             ? 0 : fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, max_side, max_cells);
+}
+
+// a kernel whose workgroups read an env's inputs while they (or others) store: no output may share a byte with an input or with
+// another output (null pointers pass: an optional buffer left out)
+struct ByteRange { const void* p; uintptr_t bytes; const char* name; };
+static int check_disjoint(smj_ctx* c, std::initializer_list<ByteRange> inputs, std::initializer_list<ByteRange> outputs) {
+  const auto meet = [](const ByteRange& a, const ByteRange& b) { return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < (uintptr_t)a.p + a.bytes; };
+  for (const ByteRange& o : outputs)
+    for (const ByteRange& i : inputs)
+      if (meet(o, i)) return fail(c, -1, "the %s range overlaps the %s range", o.name, i.name);
+  for (const ByteRange* o = outputs.begin(); o != outputs.end(); o++)
+    for (const ByteRange* q = o + 1; q != outputs.end(); q++)
+      if (meet(*o, *q)) return fail(c, -1, "the %s and %s ranges overlap", o->name, q->name);
+  return 0;
+}
+
 // every buffer of an entry is read and written in 4-byte words (null pointers pass: whether one may be null is the entry's business)
 static int check_aligned(smj_ctx* c, std::initializer_list<const void*> ptrs, const char* what) {
   uintptr_t bits = 0;
@@ -802,20 +822,13 @@ int smj_occupancy_to_distance(smj_ctx* c, const void* hit_dev, const void* miss_
   if (!c) return -1;
   if (!hit_dev || !dist2_dev) return fail(c, -1, "null hit / dist2 buffer");
   TRY(check_aligned(c, {hit_dev, miss_dev, dist2_dev, nearest_dev}, "hit / miss / dist2 / nearest buffer"));
-  if (nx < 1 || ny < 1 || nx > SMJ_EDT_MAX_SIDE || ny > SMJ_EDT_MAX_SIDE || (long long)nx * ny > SMJ_EDT_MAX_CELLS)
-    return fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, (int)SMJ_EDT_MAX_SIDE, (int)SMJ_EDT_MAX_CELLS);
+  TRY(check_cell_grid(c, nx, ny, SMJ_EDT_MAX_SIDE, SMJ_EDT_MAX_CELLS));
   if (min_hits < 1) return fail(c, -1, "min_hits %d below 1: every cell would be an obstacle", min_hits);
   if (max_dist_cells < 0) return fail(c, -1, "max_dist_cells %d is negative (0 = no bound)", max_dist_cells);
   if (unknown_is_obstacle && !miss_dev) return fail(c, -1, "unknown_is_obstacle needs the miss layer");
-  // several workgroups of an env read the grid while others store: no output may share a byte with an input or the other output
+  // several workgroups of an env read the grid while others store
   const uintptr_t bytes = (uintptr_t)c->num_envs * (uintptr_t)nx * (uintptr_t)ny * 4u;
-  const uintptr_t in[2] = {(uintptr_t)hit_dev, (uintptr_t)miss_dev}, out[2] = {(uintptr_t)dist2_dev, (uintptr_t)nearest_dev};
-  for (int o = 0; o < 2; o++) {
-    if (!out[o]) continue;
-    for (int i = 0; i < 2; i++)
-      if (in[i] && out[o] < in[i] + bytes && in[i] < out[o] + bytes) return fail(c, -1, "an output range overlaps an input range");
-  }
-  if (out[1] && out[0] < out[1] + bytes && out[1] < out[0] + bytes) return fail(c, -1, "the dist2 and nearest ranges overlap");
+  TRY(check_disjoint(c, {{hit_dev, bytes, "hit"}, {miss_dev, bytes, "miss"}}, {{dist2_dev, bytes, "dist2"}, {nearest_dev, bytes, "nearest"}}));
   HIPCHK(c, hipSetDevice(c->device));
   // no cell pair is further apart than sqrt(2) 4095 cells: a larger bound is no bound (and R * R stays an int)
   const int R = max_dist_cells >= 2 * SMJ_EDT_MAX_SIDE ? 0 : max_dist_cells;
@@ -830,22 +843,14 @@ int smj_costmap_to_navigation(smj_ctx* c, const void* cost_dev, const void* goal
   if (!c) return -1;
   if (!goal_dev || !potential_dev) return fail(c, -1, "null goal / potential buffer");
   TRY(check_aligned(c, {goal_dev, potential_dev, next_dev}, "goal / potential / next buffer"));
-  if (nx < 1 || ny < 1 || nx > SMJ_NAV_MAX_SIDE || ny > SMJ_NAV_MAX_SIDE || (long long)nx * ny > SMJ_NAV_MAX_CELLS)
-    return fail(c, -1, "bad grid %d x %d (1 <= nx, ny <= %d, nx * ny <= %d)", nx, ny, (int)SMJ_NAV_MAX_SIDE, (int)SMJ_NAV_MAX_CELLS);
+  TRY(check_cell_grid(c, nx, ny, SMJ_NAV_MAX_SIDE, SMJ_NAV_MAX_CELLS));
   if (num_goals < 1 || num_goals > SMJ_NAV_MAX_GOALS) return fail(c, -1, "num_goals %d outside [1, %d]", num_goals, (int)SMJ_NAV_MAX_GOALS);
   if (lethal < 1 || lethal > 256) return fail(c, -1, "lethal %d outside [1, 256]: below 1 no cell is passable, above 256 means 256", lethal);
   if (neutral < 1 || neutral > 255) return fail(c, -1, "neutral %d outside [1, 255]: a free step must cost something, and the potential must stay below 2^30", neutral);
-  // the workgroup of an env reads its inputs while it stores (the potential of a large grid is relaxed in place): no output may
-  // share a byte with an input or the other output
+  // the workgroup of an env reads its inputs while it stores (the potential of a large grid is relaxed in place)
   const uintptr_t cells = (uintptr_t)c->num_envs * (uintptr_t)nx * (uintptr_t)ny;
-  const uintptr_t in[2] = {(uintptr_t)cost_dev, (uintptr_t)goal_dev}, in_bytes[2] = {cells, (uintptr_t)c->num_envs * (uintptr_t)num_goals * 4u};
-  const uintptr_t out[2] = {(uintptr_t)potential_dev, (uintptr_t)next_dev}, bytes = cells * 4u;
-  for (int o = 0; o < 2; o++) {
-    if (!out[o]) continue;
-    for (int i = 0; i < 2; i++)
-      if (in[i] && out[o] < in[i] + in_bytes[i] && in[i] < out[o] + bytes) return fail(c, -1, "an output range overlaps an input range");
-  }
-  if (out[1] && out[0] < out[1] + bytes && out[1] < out[0] + bytes) return fail(c, -1, "the potential and next ranges overlap");
+  TRY(check_disjoint(c, {{cost_dev, cells, "cost"}, {goal_dev, (uintptr_t)c->num_envs * (uintptr_t)num_goals * 4u, "goal"}},
+                     {{potential_dev, cells * 4u, "potential"}, {next_dev, cells * 4u, "next"}}));
   HIPCHK(c, hipSetDevice(c->device));
   smj_launch_nav(c->num_envs, (const uint8_t*)cost_dev, (const int*)goal_dev, num_goals, nx, ny, lethal, neutral, (int*)potential_dev,
                  (int*)next_dev, (hipStream_t)stream);

@@ -10,14 +10,7 @@
 //             order in which the rows are visited does not matter.
 // With a bound R > 0 a cell whose minimum exceeds R^2 has none; offsets beyond R and rows beyond R can then be left out early.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define SMJ_EDT_HD __host__ __device__ __forceinline__
-#else
-#define SMJ_EDT_HD static inline
-#endif
+#include "smj_grid.h"   // SMJ_GRID_HD and the store's 16-byte groups
 
 // SMJ_EDT_NONE: dist2 of a cell with no obstacle (in reach); = SMJ_DIST_NONE of the public header.  The largest grid, the longest
 // side (row offsets fit int16, dist2 < 2^25), the cells of one strip (int16 offsets: 32 KiB of LDS) and the offset of "none".
@@ -25,23 +18,23 @@ enum { SMJ_EDT_NONE = 1 << 30, SMJ_EDT_MAX_CELLS = 65536, SMJ_EDT_MAX_SIDE = 409
 enum { SMJ_EDT_MASK_WORDS = SMJ_EDT_MAX_CELLS / 64 };   // the obstacle mask of a whole grid: bit c of the mask is cell c, 8 KiB
 
 // Obstacle: hit >= min_hits, or -- with unknown_is_obstacle and a miss layer -- a cell no ray has seen (hit == 0 && miss == 0).
-SMJ_EDT_HD bool smj_edt_obstacle(int hit, int miss, int have_miss, int min_hits, int unknown_is_obstacle) {
+SMJ_GRID_HD bool smj_edt_obstacle(int hit, int miss, int have_miss, int min_hits, int unknown_is_obstacle) {
   return hit >= min_hits || (unknown_is_obstacle && have_miss && hit == 0 && miss == 0);
 }
 
 // Column strips.  A workgroup holds the offsets of [ny] x [w] cells, ny w <= SMJ_EDT_STRIP_CELLS: the fewest strips that allow it,
 // of equal width (the last one may be narrower).  ny <= 4096 leaves w >= 4.  128 x 128 is one strip, 256 x 256 four of 64 columns.
 struct smj_edt_strip_t { int c0, w; };
-SMJ_EDT_HD int smj_edt_strip_width(int nx, int ny) {
+SMJ_GRID_HD int smj_edt_strip_width(int nx, int ny) {
   const int wmax = SMJ_EDT_STRIP_CELLS / ny;
   const int n = (nx + wmax - 1) / wmax;
   return (nx + n - 1) / n;
 }
-SMJ_EDT_HD int smj_edt_strips(int nx, int ny) {
+SMJ_GRID_HD int smj_edt_strips(int nx, int ny) {
   const int w = smj_edt_strip_width(nx, ny);
   return (nx + w - 1) / w;
 }
-SMJ_EDT_HD smj_edt_strip_t smj_edt_strip(int nx, int ny, int s) {
+SMJ_GRID_HD smj_edt_strip_t smj_edt_strip(int nx, int ny, int s) {
   smj_edt_strip_t t;
   const int w = smj_edt_strip_width(nx, ny);
   t.c0 = s * w;
@@ -50,7 +43,7 @@ SMJ_EDT_HD smj_edt_strip_t smj_edt_strip(int nx, int ny, int s) {
 }
 
 // The highest set bit of the mask in [lo, pos], or -1; the lowest set bit in [pos, hi], or -1.  lo <= pos <= hi, all inside the mask.
-SMJ_EDT_HD int smj_edt_prev(const unsigned long long* mask, int lo, int pos) {
+SMJ_GRID_HD int smj_edt_prev(const unsigned long long* mask, int lo, int pos) {
   int wi = pos >> 6;
   const int wlo = lo >> 6;
   unsigned long long bits = mask[wi] & (~0ull >> (63 - (pos & 63)));
@@ -61,7 +54,7 @@ SMJ_EDT_HD int smj_edt_prev(const unsigned long long* mask, int lo, int pos) {
     bits = mask[--wi];
   }
 }
-SMJ_EDT_HD int smj_edt_next(const unsigned long long* mask, int pos, int hi) {
+SMJ_GRID_HD int smj_edt_next(const unsigned long long* mask, int pos, int hi) {
   int wi = pos >> 6;
   const int whi = hi >> 6;
   unsigned long long bits = mask[wi] & (~0ull << (pos & 63));
@@ -76,7 +69,7 @@ SMJ_EDT_HD int smj_edt_next(const unsigned long long* mask, int pos, int hi) {
 // The row rule: the signed offset from cell (y, x) to the nearest obstacle of row y, ties to the left; SMJ_EDT_NO_OFF if the row has
 // none -- or, with R > 0, none within R cells (such a one cannot give dist2 <= R^2).  The mask is that of the whole grid, so the
 // search crosses the edges of a strip.
-SMJ_EDT_HD int smj_edt_row_offset(const unsigned long long* mask, int nx, int y, int x, int R) {
+SMJ_GRID_HD int smj_edt_row_offset(const unsigned long long* mask, int nx, int y, int x, int R) {
   const int row = y * nx, pos = row + x;
   int lo = row, hi = row + nx - 1;
   if (R > 0) {
@@ -94,7 +87,7 @@ SMJ_EDT_HD int smj_edt_row_offset(const unsigned long long* mask, int nx, int y,
 // search goes outward from row y, the row above before the row below, and stops at the first dy with dy^2 > best (strictly: at
 // dy^2 == best the cell straight above still wins by its smaller index), with dy > R, or with both rows outside [jlo, jhi].
 // Candidates are compared as (dist2, index), so the result does not depend on that order.  R > 0: a minimum above R^2 is none.
-SMJ_EDT_HD void smj_edt_column(const int16_t* off, int stride, int nx, int y, int x, int jlo, int jhi, int R, int* dist2, int* nearest) {
+SMJ_GRID_HD void smj_edt_column(const int16_t* off, int stride, int nx, int y, int x, int jlo, int jhi, int R, int* dist2, int* nearest) {
   int best = SMJ_EDT_NONE, at = -1;
   if (jlo <= jhi) {
     if (y >= jlo && y <= jhi) {
@@ -125,13 +118,6 @@ SMJ_EDT_HD void smj_edt_column(const int16_t* off, int stride, int nx, int y, in
   *dist2 = best;
   *nearest = at;
 }
-
-// The store's 16-byte groups.  A row segment of w cells whose first cell sits `al` words (0 .. 3) past a 16-byte boundary is covered
-// by the groups k = 0 .. smj_edt_groups(w) - 1, group k holding the segment's cells first .. first + 3 with first = 4 k - al, cut to
-// [0, w): every cell is in exactly one group, a group inside the segment starts on a 16-byte boundary, and a group with
-// first >= w is empty (the count is that of al = 3).
-SMJ_EDT_HD int smj_edt_groups(int w) { return (w + 6) >> 2; }
-SMJ_EDT_HD int smj_edt_group_first(int k, int al) { return 4 * k - al; }
 
 #if defined(__HIPCC__)
 // Launch (smj_edt.hip).  miss and nearest may be null.

@@ -93,13 +93,13 @@ __global__ __launch_bounds__(EDT_THREADS) void smj_edt_kernel(const EdtArgs a) {
   // (3) the column pass: one 16-byte group of dist2 per thread and step
   int* d2 = a.dist2 + e0;
   int* nr = a.nearest ? a.nearest + e0 : nullptr;
-  const int gmax = smj_edt_groups(s.w);   // groups a row segment of w cells can touch, whatever its alignment
+  const int gmax = smj_grid_groups(s.w);   // groups a row segment of w cells can touch, whatever its alignment
   const int nitem = a.ny * gmax;
   for (int t = tid; t < nitem; t += EDT_THREADS) {
     const int y = t / gmax, k = t - y * gmax;
     const int g0 = y * a.nx + s.c0;   // the row segment's first cell
     const int al = (int)(((uintptr_t)(d2 + g0) >> 2) & 3u);   // its word offset inside a 16-byte group
-    const int l0 = smj_edt_group_first(k, al);   // first cell of the group, relative to the segment
+    const int l0 = smj_grid_group_first(k, al);   // first cell of the group, relative to the segment
     if (l0 >= s.w) continue;
     int d[4] = {0, 0, 0, 0}, n[4] = {0, 0, 0, 0};
     for (int i = 0; i < 4; i++) {

@@ -1,6 +1,6 @@
 // Exact cost-to-goal fields (navigation functions) of costmaps (smj_costmap_to_navigation, include/smj_navigation.h): the passability
-// predicate, the move cost, the diagonal rule, "relax one cell from its neighbours", "next of one cell", the sweep schedule and the
-// store's groups as plain inline functions.  The kernel of smj_nav.hip calls exactly these; the header also compiles under a host
+// predicate, the move cost, the diagonal rule, "relax one cell from its neighbours", "next of one cell" and the sweep schedule as plain
+// inline functions (the store's groups: smj_grid.h).  The kernel of smj_nav.hip calls exactly these; the header also compiles under a host
 // compiler, so tests/nav/nav_check.cpp runs the shipped code serially against its own Dijkstra.  Integers only.
 //
 // The rule.  A cell c is passable iff cost[c] < lethal; its weight is w(c) = neutral + cost[c] (1 .. 510).  Moves go to the 8
@@ -14,14 +14,7 @@
 // and "weight".  The potential is reached through an accessor P with int get(int c) const and void set(int c, int v): LDS or global
 // memory in the kernel, a vector in the host harness.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define SMJ_NAV_HD __host__ __device__ __forceinline__
-#else
-#define SMJ_NAV_HD static inline
-#endif
+#include "smj_grid.h"   // SMJ_GRID_HD and the store's 16-byte groups
 
 // SMJ_NAV_NONE: the potential of a cell without a path to a goal -- the public header's macro, token for token, so that a translation
 // unit may include both.  The largest grid, the longest side, the most goals per env, and the cells whose potential fits LDS (int32:
@@ -30,28 +23,28 @@
 enum { SMJ_NAV_MAX_CELLS = 65536, SMJ_NAV_MAX_SIDE = 4096, SMJ_NAV_MAX_GOALS = 64, SMJ_NAV_LDS_CELLS = 16384 };
 
 // Passable iff cost < lethal; the stored weight, 0 = impassable.
-SMJ_NAV_HD bool smj_nav_passable(int cost, int lethal) { return cost < lethal; }
-SMJ_NAV_HD uint16_t smj_nav_weight(int cost, int lethal, int neutral) { return smj_nav_passable(cost, lethal) ? (uint16_t)(neutral + cost) : (uint16_t)0; }
+SMJ_GRID_HD bool smj_nav_passable(int cost, int lethal) { return cost < lethal; }
+SMJ_GRID_HD uint16_t smj_nav_weight(int cost, int lethal, int neutral) { return smj_nav_passable(cost, lethal) ? (uint16_t)(neutral + cost) : (uint16_t)0; }
 
 // The cost of a move between two passable cells of weights wa, wb.
-SMJ_NAV_HD int smj_nav_move(int wa, int wb, bool diagonal) { return (diagonal ? 7 : 5) * (wa + wb); }
+SMJ_GRID_HD int smj_nav_move(int wa, int wb, bool diagonal) { return (diagonal ? 7 : 5) * (wa + wb); }
 
 // The diagonal rule: the move exists iff the two cells it passes between are passable (their stored weights are not 0).
-SMJ_NAV_HD bool smj_nav_diagonal_open(int w_row_neighbour, int w_col_neighbour) { return w_row_neighbour != 0 && w_col_neighbour != 0; }
+SMJ_GRID_HD bool smj_nav_diagonal_open(int w_row_neighbour, int w_col_neighbour) { return w_row_neighbour != 0 && w_col_neighbour != 0; }
 
 // Is a goal entry used: inside the grid and on a passable cell.
-SMJ_NAV_HD bool smj_nav_goal_used(int g, int ncell, const uint16_t* w) { return g >= 0 && g < ncell && w[g] != 0; }
+SMJ_GRID_HD bool smj_nav_goal_used(int g, int ncell, const uint16_t* w) { return g >= 0 && g < ncell && w[g] != 0; }
 
 // The 8 neighbours in ascending linear index: k = 0 .. 7 -> (dy, dx); odd |dy| + |dx| = axial.
-SMJ_NAV_HD int smj_nav_dy(int k) { return k < 3 ? -1 : k < 5 ? 0 : 1; }
-SMJ_NAV_HD int smj_nav_dx(int k) { return k < 3 ? k - 1 : k == 3 ? -1 : k == 4 ? 1 : k - 6; }
+SMJ_GRID_HD int smj_nav_dy(int k) { return k < 3 ? -1 : k < 5 ? 0 : 1; }
+SMJ_GRID_HD int smj_nav_dx(int k) { return k < 3 ? k - 1 : k == 3 ? -1 : k == 4 ? 1 : k - 6; }
 
 // The 8 neighbours of (y, x): n[k] is neighbour k's linear index -- the cell's own where the neighbour lies outside the grid, so that
 // every n[k] may be read without a branch -- and wn[k] its stored weight, 0 outside the grid, with a diagonal neighbour whose move
 // does not exist set to 0 as well: wn[k] != 0 iff the move from (y, x) to neighbour k exists (given that (y, x) itself is passable).
 // All eight reads are issued before any is used: a walk is a chain of dependent cells, and its pace is the latency of one read.
 struct smj_nav_nbr_t { int n[8], wn[8]; };
-SMJ_NAV_HD smj_nav_nbr_t smj_nav_neighbours(const uint16_t* w, int nx, int ny, int y, int x) {
+SMJ_GRID_HD smj_nav_nbr_t smj_nav_neighbours(const uint16_t* w, int nx, int ny, int y, int x) {
   smj_nav_nbr_t b;
   const int c = y * nx + x;
   const int up = y > 0 ? -nx : 0, down = y + 1 < ny ? nx : 0, left = x > 0 ? -1 : 0, right = x + 1 < nx ? 1 : 0;
@@ -76,7 +69,7 @@ SMJ_NAV_HD smj_nav_nbr_t smj_nav_neighbours(const uint16_t* w, int nx, int ny, i
 // neighbours' current values (stale ones are fine: values only fall).  Returns whether the cell's value fell.  An impassable cell
 // never changes; a goal holds 0 and cannot fall.
 template <class P>
-SMJ_NAV_HD bool smj_nav_relax(P& pot, const uint16_t* w, int nx, int ny, int y, int x) {
+SMJ_GRID_HD bool smj_nav_relax(P& pot, const uint16_t* w, int nx, int ny, int y, int x) {
   const int c = y * nx + x, wc = w[c];
   if (!wc) return false;
   const smj_nav_nbr_t b = smj_nav_neighbours(w, nx, ny, y, x);
@@ -95,7 +88,7 @@ SMJ_NAV_HD bool smj_nav_relax(P& pot, const uint16_t* w, int nx, int ny, int y, 
 // next of one cell, from the converged potential: -1 where there is no path, the cell itself on a goal (potential 0: every move
 // costs at least 10), else the neighbour with the smallest move + potential, the first of equals in ascending linear index.
 template <class P>
-SMJ_NAV_HD int smj_nav_next(const P& pot, const uint16_t* w, int nx, int ny, int y, int x) {
+SMJ_GRID_HD int smj_nav_next(const P& pot, const uint16_t* w, int nx, int ny, int y, int x) {
   const int c = y * nx + x, wc = w[c];
   if (!wc) return -1;
   const int own = pot.get(c);
@@ -121,18 +114,18 @@ SMJ_NAV_HD int smj_nav_next(const P& pot, const uint16_t* w, int nx, int ny, int
 // smj_nav_lines: the lines of sweep s; smj_nav_line_len: their length; smj_nav_line_cell: the (y, x) of position i on line l;
 // smj_nav_runs: the runs per line; run r of the sweep is run r % runs of line r / runs, the positions [i0, i1) of smj_nav_run.
 enum { SMJ_NAV_MIN_RUN = 128 };
-SMJ_NAV_HD int smj_nav_lines(int nx, int ny, int s) { return s & 1 ? nx : ny; }
-SMJ_NAV_HD int smj_nav_line_len(int nx, int ny, int s) { return s & 1 ? ny : nx; }
-SMJ_NAV_HD void smj_nav_line_cell(int s, int l, int i, int* y, int* x) {
+SMJ_GRID_HD int smj_nav_lines(int nx, int ny, int s) { return s & 1 ? nx : ny; }
+SMJ_GRID_HD int smj_nav_line_len(int nx, int ny, int s) { return s & 1 ? ny : nx; }
+SMJ_GRID_HD void smj_nav_line_cell(int s, int l, int i, int* y, int* x) {
   if (s & 1) { *y = i; *x = l; }
   else { *y = l; *x = i; }
 }
-SMJ_NAV_HD int smj_nav_runs(int nx, int ny, int s, int nthreads) {
+SMJ_GRID_HD int smj_nav_runs(int nx, int ny, int s, int nthreads) {
   const int per_line = nthreads / smj_nav_lines(nx, ny, s), by_len = smj_nav_line_len(nx, ny, s) / SMJ_NAV_MIN_RUN;
   const int r = per_line < by_len ? per_line : by_len;
   return r < 1 ? 1 : r;
 }
-SMJ_NAV_HD void smj_nav_run(int nx, int ny, int s, int runs, int r, int* l, int* i0, int* i1) {
+SMJ_GRID_HD void smj_nav_run(int nx, int ny, int s, int runs, int r, int* l, int* i0, int* i1) {
   const int len = smj_nav_line_len(nx, ny, s), per = (len + runs - 1) / runs;
   *l = r / runs;
   *i0 = (r - *l * runs) * per;
@@ -141,7 +134,7 @@ SMJ_NAV_HD void smj_nav_run(int nx, int ny, int s, int runs, int r, int* l, int*
 // One thread's walk of the positions [i0, i1) of line l in sweep s: forward over i0 .. i1 - 1, backward over i1 - 2 .. i0.  Returns
 // whether any cell fell.
 template <class P>
-SMJ_NAV_HD bool smj_nav_walk_run(P& pot, const uint16_t* w, int nx, int ny, int s, int l, int i0, int i1) {
+SMJ_GRID_HD bool smj_nav_walk_run(P& pot, const uint16_t* w, int nx, int ny, int s, int l, int i0, int i1) {
   bool changed = false;
   int y, x;
   for (int i = i0; i < i1; i++) {
@@ -156,13 +149,7 @@ SMJ_NAV_HD bool smj_nav_walk_run(P& pot, const uint16_t* w, int nx, int ny, int 
 }
 // The hard bound on the number of sweeps: every sweep relaxes every cell at least once from values no older than the previous
 // sweep's, so after k sweeps every cell whose cheapest path has at most k moves is final, and a path has fewer than nx ny moves.
-SMJ_NAV_HD int smj_nav_max_sweeps(int nx, int ny) { return nx * ny; }
-
-// The store's 16-byte groups over an env's ncell consecutive cells, whose first cell sits `al` words (0 .. 3) past a 16-byte
-// boundary: group k holds the cells first .. first + 3 with first = 4 k - al, cut to [0, ncell); every cell is in exactly one group
-// and a whole group starts on a 16-byte boundary.
-SMJ_NAV_HD int smj_nav_groups(int ncell) { return (ncell + 6) >> 2; }
-SMJ_NAV_HD int smj_nav_group_first(int k, int al) { return 4 * k - al; }
+SMJ_GRID_HD int smj_nav_max_sweeps(int nx, int ny) { return nx * ny; }
 
 #if defined(__HIPCC__)
 // Launch (smj_nav.hip).  cost and next may be null.

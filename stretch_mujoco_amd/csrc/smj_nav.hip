@@ -80,9 +80,9 @@ struct NavPot {
 template <class F>
 __device__ __forceinline__ void nav_store(int* out, int ncell, int tid, F value) {
   const int al = (int)(((uintptr_t)out >> 2) & 3u);
-  const int ngroups = smj_nav_groups(ncell);
+  const int ngroups = smj_grid_groups(ncell);
   for (int k = tid; k < ngroups; k += NAV_THREADS) {
-    const int first = smj_nav_group_first(k, al);
+    const int first = smj_grid_group_first(k, al);
     if (first >= ncell) continue;
     if (first >= 0 && first + 4 <= ncell) {
       *reinterpret_cast<int4*>(out + first) = make_int4(value(first), value(first + 1), value(first + 2), value(first + 3));

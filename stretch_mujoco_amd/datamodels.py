@@ -186,24 +186,14 @@ class StatusStretchDistanceField:
         """fp32 [B, ny, nx]: sqrt(dist2) cell in metres, inf where there is no obstacle in reach."""
         import torch
 
-        d = torch.sqrt(self.dist2.to(torch.float32)) * float(self.cell)
-        return torch.where(self.dist2 >= self.NONE, torch.tensor(float("inf"), dtype=torch.float32, device=d.device), d)
+        return _inf_where_none(torch.sqrt(self.dist2.to(torch.float32)) * float(self.cell), self.dist2, self.NONE)
 
     def nearest_offset(self):
         """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell to its nearest obstacle, zeros where there is none.  Needs
         pull_distance_field(nearest=True)."""
-        import torch
-
         if self.nearest is None:
             raise ValueError("nearest_offset() needs pull_distance_field(nearest=True)")
-        ny, nx = self.nearest.shape[-2:]
-        iy = torch.arange(ny, dtype=torch.int32, device=self.nearest.device).view(1, ny, 1)
-        ix = torch.arange(nx, dtype=torch.int32, device=self.nearest.device).view(1, 1, nx)
-        have = self.nearest >= 0
-        n = torch.where(have, self.nearest, 0)
-        dy = torch.where(have, torch.div(n, nx, rounding_mode="floor") - iy, 0)
-        dx = torch.where(have, n % nx - ix, 0)
-        return torch.stack((dy, dx), -1).to(torch.int32)
+        return offsets_of_cells(self.nearest)
 
     def inflated_cost(self, inscribed_radius: float, inflation_radius: float, cost_scaling_factor: float = 10.0):
         """uint8 [B, ny, nx] by the costmap convention (costmap_2d's inflation layer): 254 on an obstacle, 253 within
@@ -220,6 +210,24 @@ class StatusStretchDistanceField:
         cost = torch.where(self.dist2 == 0, torch.full_like(cost, 254.0), cost)
         cost = torch.where(d > r_inf, torch.zeros_like(cost), cost)
         return cost.to(torch.uint8)
+
+
+def offsets_of_cells(index):
+    """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell (iy, ix) of a grid [B, ny, nx] to the cell its entry names as a linear
+    index iy nx + ix; zeros where the entry is negative (none).  On the index's device, no host synchronisation."""
+    import torch
+
+    ny, nx = index.shape[-2:]
+    iy = torch.arange(ny, dtype=torch.int32, device=index.device).view(1, ny, 1)
+    ix = torch.arange(nx, dtype=torch.int32, device=index.device).view(1, 1, nx)
+    n = index.clamp(min=0)
+    off = torch.stack((torch.div(n, nx, rounding_mode="floor") - iy, n % nx - ix), -1)
+    return torch.where((index >= 0).unsqueeze(-1), off, 0).to(torch.int32)
+
+
+def _inf_where_none(metres, raw, none):
+    """`metres` (fp32) with inf where the integer field `raw` holds its NONE or more: no obstacle in reach, no path."""
+    return metres.masked_fill(raw >= none, float("inf"))
 
 
 def cells_of_points(points, origin, cell, ny, nx):
@@ -256,24 +264,14 @@ class StatusStretchNavigationField:
         where there is no path."""
         import torch
 
-        d = self.potential.to(torch.float32) * (float(self.cell) / (10.0 * float(self.neutral)))
-        return torch.where(self.potential >= self.NONE, torch.tensor(float("inf"), dtype=torch.float32, device=d.device), d)
+        return _inf_where_none(self.potential.to(torch.float32) * (float(self.cell) / (10.0 * float(self.neutral))), self.potential, self.NONE)
 
     def next_offset(self):
         """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell to the neighbour to step to, zeros on goals and where there is no
         path.  Needs pull_navigation_field(next=True)."""
-        import torch
-
         if self.next is None:
             raise ValueError("next_offset() needs pull_navigation_field(next=True)")
-        ny, nx = self.next.shape[-2:]
-        iy = torch.arange(ny, dtype=torch.int32, device=self.next.device).view(1, ny, 1)
-        ix = torch.arange(nx, dtype=torch.int32, device=self.next.device).view(1, 1, nx)
-        have = self.next >= 0
-        n = torch.where(have, self.next, 0)
-        dy = torch.where(have, torch.div(n, nx, rounding_mode="floor") - iy, 0)
-        dx = torch.where(have, n % nx - ix, 0)
-        return torch.stack((dy, dx), -1).to(torch.int32)
+        return offsets_of_cells(self.next)
 
     def heading(self):
         """fp32 [B, ny, nx]: atan2(dy, dx) of next_offset(), the direction to drive in the grid's frame; NaN on goals and where there

@@ -374,6 +374,50 @@ class StretchBatchSimulator:
             bufs = cache[key] = make()
         return bufs
 
+    def _cached_int_pair(self, cache, key, ny, nx, second, *extra):
+        """The int32 buffers [first, second, *extra] of `key`: [B, ny, nx] twice, the second made by the first call that asks for it
+        (`second`), and [B, *shape] per shape in `extra`.  Returns the list and this call's second buffer or None."""
+        new = lambda *shape: torch.empty(self.num_envs, *shape, dtype=torch.int32, device=self.device)
+        bufs = self._cached(cache, key, lambda: [new(ny, nx), None, *(new(*shape) for shape in extra)])
+        if second and bufs[1] is None:
+            bufs[1] = new(ny, nx)
+        return bufs, bufs[1] if second else None
+
+    @staticmethod
+    def _upstream_kwargs(kwargs, upstream, called, cell, origin):
+        """The keywords of the pull a grid entry runs when handed no input (`called`): cell and origin join them; an entry that
+        was handed its input takes none.  `upstream`: that pull's name and the argument whose None triggers it."""
+        if called:
+            kwargs.update({k: v for k, v in (("cell", cell), ("origin", origin)) if v is not None})
+        elif kwargs:
+            raise ValueError(f"{sorted(kwargs)}: keywords of {upstream[0]}, which is called only for {upstream[1]}=None")
+
+    @staticmethod
+    def _origin_cell(status, origin, cell):
+        """((x0, y0), cell) of a grid entry's input, cell checked: those of the Status* object `status` (the keywords are refused
+        then) or, for a bare tensor (status None), the keywords, (0, 0) and 1.0 if absent."""
+        if status is not None:
+            if cell is not None or origin is not None:
+                raise ValueError(f"cell and origin come from the {type(status).__name__}")
+            x0y0, cell = tuple(status.origin), float(status.cell)
+        else:
+            try:
+                x0y0 = (0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
+                cell = 1.0 if cell is None else float(cell)
+            except (TypeError, ValueError):
+                raise ValueError("origin = (x0, y0), cell a number") from None
+            if len(x0y0) != 2 or not (np.isfinite(x0y0[0]) and np.isfinite(x0y0[1])):
+                raise ValueError("origin = (x0, y0), finite")
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        return x0y0, cell
+
+    @staticmethod
+    def _check_cell_count(what, ny, nx):
+        """The limit of the integer-grid kernels (SMJ_EDT_MAX_*, SMJ_NAV_MAX_*)."""
+        if ny < 1 or nx < 1 or ny > 4096 or nx > 4096 or ny * nx > 65536:
+            raise ValueError(f"{what}: 1 <= ny, nx <= 4096 and ny * nx <= 65536")
+
     @_require_connection
     def pull_point_cloud(self, camera: StretchCameras, frame: str = "camera", stride: int = 1, render: bool = True,
                          auto_rotate: bool = False) -> torch.Tensor:
@@ -515,41 +559,26 @@ class StretchBatchSimulator:
         if min_hits < 1:
             raise ValueError("min_hits must be >= 1")
         miss = None
+        self._upstream_kwargs(occupancy_kwargs, ("pull_occupancy_grid", "grid"), grid is None, cell, origin)
         if grid is None:
-            if cell is not None:
-                occupancy_kwargs["cell"] = cell
-            if origin is not None:
-                occupancy_kwargs["origin"] = origin
             grid = self.pull_occupancy_grid(**occupancy_kwargs)
             cell = origin = None
-        elif occupancy_kwargs:
-            raise ValueError(f"{sorted(occupancy_kwargs)}: keywords of pull_occupancy_grid, which is called only for grid=None")
         if isinstance(grid, StatusStretchOccupancyGrid):
-            if cell is not None or origin is not None:
-                raise ValueError("cell and origin come from the StatusStretchOccupancyGrid")
-            hit, miss, frame, x0y0, cell = grid.hit, grid.miss, grid.frame, tuple(grid.origin), float(grid.cell)
+            x0y0, cell = self._origin_cell(grid, origin, cell)
+            hit, miss, frame = grid.hit, grid.miss, grid.frame
         else:
             if not isinstance(grid, torch.Tensor) or grid.dtype not in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
                 raise ValueError("grid: None, a StatusStretchOccupancyGrid, or a bool / integer tensor [B, ny, nx]")
             if min_hits != 1 or unknown_is_obstacle:
                 raise ValueError("a mask has no counts and no miss layer: min_hits = 1, unknown_is_obstacle = False")
-            try:
-                x0y0 = (0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
-                cell = 1.0 if cell is None else float(cell)
-            except (TypeError, ValueError):
-                raise ValueError("origin = (x0, y0), cell a number") from None
-            if len(x0y0) != 2 or not (np.isfinite(x0y0[0]) and np.isfinite(x0y0[1])):
-                raise ValueError("origin = (x0, y0), finite")
+            x0y0, cell = self._origin_cell(None, origin, cell)
             hit, frame = (grid != 0).to(device=self.device, dtype=torch.int32).contiguous(), "grid"
-        if not (np.isfinite(cell) and cell > 0):
-            raise ValueError("cell must be finite and > 0")
         for t in (hit, miss):
             if t is not None and (t.dim() != 3 or t.shape[0] != self.num_envs or t.dtype != torch.int32 or not t.is_contiguous()
                                   or t.device != self.device or (miss is not None and t.shape != hit.shape)):
                 raise ValueError(f"grid: contiguous int32 [num_envs = {self.num_envs}, ny, nx] on {self.device}")
         ny, nx = int(hit.shape[1]), int(hit.shape[2])
-        if ny < 1 or nx < 1 or ny > 4096 or nx > 4096 or ny * nx > 65536:
-            raise ValueError("grid: 1 <= ny, nx <= 4096 and ny * nx <= 65536")
+        self._check_cell_count("grid", ny, nx)
         if unknown_is_obstacle and miss is None:
             raise ValueError("unknown_is_obstacle needs a miss layer")
         R = 0
@@ -558,10 +587,7 @@ class StretchBatchSimulator:
             if not (np.isfinite(max_distance) and max_distance > 0):
                 raise ValueError("max_distance: metres, finite and > 0 (None = no bound)")
             R = int(min(math.ceil(max_distance / cell), 8192))   # beyond the longest diagonal every bound is none
-        bufs = self._cached(self._dist, (ny, nx), lambda: [torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device), None])
-        if nearest and bufs[1] is None:
-            bufs[1] = torch.empty(self.num_envs, ny, nx, dtype=torch.int32, device=self.device)
-        near = bufs[1] if nearest else None
+        bufs, near = self._cached_int_pair(self._dist, (ny, nx), ny, nx, nearest)
         rc = self._L.smj_occupancy_to_distance(self._ctx, ctypes.c_void_p(hit.data_ptr()), ctypes.c_void_p(miss.data_ptr()) if miss is not None else None,
                                                nx, ny, min_hits, int(bool(unknown_is_obstacle)), R, ctypes.c_void_p(bufs[0].data_ptr()),
                                                ctypes.c_void_p(near.data_ptr()) if near is not None else None, self._stream())
@@ -620,48 +646,29 @@ class StretchBatchSimulator:
             r_ins, r_inf, k = float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor)
             if not (0 <= r_ins <= r_inf < float("inf")) or not r_inf > 0 or not k >= 0:
                 raise ValueError("0 <= inscribed_radius <= inflation_radius, inflation_radius > 0, both finite; cost_scaling_factor >= 0")
+        if cost is None and "max_distance" in distance_kwargs:
+            raise ValueError("max_distance is the inflation_radius here")
+        self._upstream_kwargs(distance_kwargs, ("pull_distance_field", "cost"), cost is None, cell, origin)
         if cost is None:
-            if "max_distance" in distance_kwargs:
-                raise ValueError("max_distance is the inflation_radius here")
-            if cell is not None:
-                distance_kwargs["cell"] = cell
-            if origin is not None:
-                distance_kwargs["origin"] = origin
             cost = self.pull_distance_field(max_distance=r_inf, **distance_kwargs)
             cell = origin = None
-        elif distance_kwargs:
-            raise ValueError(f"{sorted(distance_kwargs)}: keywords of pull_distance_field, which is called only for cost=None")
         if isinstance(cost, StatusStretchDistanceField):
-            if cell is not None or origin is not None:
-                raise ValueError("cell and origin come from the StatusStretchDistanceField")
             df = cost
-            frame, x0y0, cell = df.frame, tuple(df.origin), float(df.cell)
+            x0y0, cell = self._origin_cell(df, origin, cell)
+            frame = df.frame
             if df.dist2.dim() != 3 or df.dist2.shape[0] != B or df.dist2.device != dev:
                 raise ValueError(f"cost: a distance field [num_envs = {B}, ny, nx] on {dev}")
             cost = df.inflated_cost(r_ins, r_inf, k)
         else:
             if not isinstance(cost, torch.Tensor) or cost.dtype != torch.uint8 or cost.dim() != 3 or cost.shape[0] != B:
                 raise ValueError(f"cost: None, a StatusStretchDistanceField, or a uint8 tensor [num_envs = {B}, ny, nx]")
-            try:
-                x0y0 = (0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
-                cell = 1.0 if cell is None else float(cell)
-            except (TypeError, ValueError):
-                raise ValueError("origin = (x0, y0), cell a number") from None
-            if len(x0y0) != 2 or not (np.isfinite(x0y0[0]) and np.isfinite(x0y0[1])):
-                raise ValueError("origin = (x0, y0), finite")
+            x0y0, cell = self._origin_cell(None, origin, cell)
             frame = "grid"
-        if not (np.isfinite(cell) and cell > 0):
-            raise ValueError("cell must be finite and > 0")
         ny, nx = int(cost.shape[1]), int(cost.shape[2])
-        if ny < 1 or nx < 1 or ny > 4096 or nx > 4096 or ny * nx > 65536:
-            raise ValueError("cost: 1 <= ny, nx <= 4096 and ny * nx <= 65536")
+        self._check_cell_count("cost", ny, nx)
         cost = cost.to(device=dev).contiguous()
         G = int(g.shape[1])
-        bufs = self._cached(self._nav, (ny, nx, G), lambda: [torch.empty(B, ny, nx, dtype=torch.int32, device=dev), None,
-                                                            torch.empty(B, G, dtype=torch.int32, device=dev)])
-        if next and bufs[1] is None:
-            bufs[1] = torch.empty(B, ny, nx, dtype=torch.int32, device=dev)
-        nxt = bufs[1] if next else None
+        bufs, nxt = self._cached_int_pair(self._nav, (ny, nx, G), ny, nx, next, (G,))
         if g.is_floating_point():
             bufs[2].copy_(cells_of_points(g, x0y0, cell, ny, nx))
         else:

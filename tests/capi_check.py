@@ -1,4 +1,4 @@
-"""What the C-API tests of the perception entries share (tests/test_{point_cloud,height_map,occupancy,distance}_capi.py): reading the
+"""What the C-API tests of the perception entries share (tests/test_{point_cloud,height_map,occupancy,distance,navigation}_capi.py): reading the
 headers of include/ and csrc/, and the assertions that hold a header, the loader (stretch_mujoco_amd/lib.py) and the library together."""
 import ctypes
 import os
@@ -29,11 +29,12 @@ def declared(text):
 
 def header_and_loader_agree(name, exports, entry):
     """The header declares the entry and nothing else, the loader lists it, no other header declares it, and the export tuples of
-    lib.py are disjoint."""
+    lib.py -- every module attribute named *EXPORTS, so that a new one cannot be left out -- are disjoint."""
     assert declared(header(name)) == sorted(exports) == [entry]
     others = [n for n in sorted(os.listdir(os.path.join(ROOT, "include"))) if n != name]
     assert entry not in sum((declared(header(n)) for n in others), [])
-    groups = [lib.EXPORTS, lib.POINT_EXPORTS, lib.HEIGHTMAP_EXPORTS, lib.OCCUPANCY_EXPORTS, lib.DISTANCE_EXPORTS]
+    groups = [getattr(lib, a) for a in sorted(dir(lib)) if a.endswith("EXPORTS")]
+    assert len(groups) >= 7 and any(g is exports for g in groups)
     for i, a in enumerate(groups):
         for b in groups[i + 1:]:
             assert not set(a) & set(b), (a, b)

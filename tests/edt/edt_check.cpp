@@ -59,12 +59,12 @@ static Field emulate(const std::vector<int>& hit, const std::vector<int>* miss, 
       off[t] = (int16_t)o;
       if (o != SMJ_EDT_NO_OFF) { jlo = y < jlo ? y : jlo; jhi = y > jhi ? y : jhi; }
     }
-    const int gmax = smj_edt_groups(s.w);
+    const int gmax = smj_grid_groups(s.w);
     for (int t = 0; t < ny * gmax; t++) {
       const int y = t / gmax, k = t - y * gmax;
       const int g0 = y * nx + s.c0;
       const int al = (base_words + g0) & 3;
-      const int l0 = smj_edt_group_first(k, al);
+      const int l0 = smj_grid_group_first(k, al);
       if (l0 >= s.w) continue;
       if (l0 >= 0 && l0 + 4 <= s.w) {
         CHECK(((base_words + g0 + l0) & 3) == 0, "a whole group off its 16-byte boundary");
@@ -121,16 +121,7 @@ static void check_pieces() {
     for (int c = hi; c >= pos; c--) if (m[c >> 6] >> (c & 63) & 1) nw = c;
     CHECK(smj_edt_prev(m.data(), lo, pos) == pw && smj_edt_next(m.data(), pos, hi) == nw, "bit search [%d, %d] from %d", lo, hi, pos);
   }
-  for (int w = 1; w <= 70; w++)
-    for (int al = 0; al < 4; al++) {
-      std::vector<int> seen(w, 0);
-      for (int k = 0; k < smj_edt_groups(w); k++)
-        for (int i = 0; i < 4; i++) {
-          const int lx = smj_edt_group_first(k, al) + i;
-          if (lx >= 0 && lx < w) seen[lx]++;
-        }
-      for (int v : seen) CHECK(v == 1, "groups of w %d al %d", w, al);
-    }
+  check_store_groups<70>(smj_grid_groups, smj_grid_group_first);
 }
 
 int main() {

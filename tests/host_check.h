@@ -1,5 +1,5 @@
-// What the host check programs of the device headers share (tests/{points,hmap,occ,edt}/*_check.cpp): the CHECK macro with its
-// failure counter, the special floats and bit casts, and a pose of fp32 numbers with a seeded random one.
+// What the host check programs of the device headers share (tests/{points,hmap,occ,edt,nav}/*_check.cpp): the CHECK macro with its
+// failure counter, the special floats and bit casts, a pose of fp32 numbers with a seeded random one, the cover of the store groups.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -36,4 +36,17 @@ static inline Pose random_pose(std::mt19937& g, double reach) {
   for (int k = 0; k < 9; k++) P.m[k] = (float)R[k];
   for (int k = 0; k < 3; k++) P.p[k] = (float)t(g);
   return P;
+}
+
+// The store's groups (csrc/smj_grid.h, handed in so that this header needs none of the device headers): for every run of
+// n = 1 .. NMAX cells and every alignment al = 0 .. 3, each index in [0, n) lies in exactly one of the groups k = 0 .. groups(n) - 1.
+template <int NMAX, class Groups, class First>
+static void check_store_groups(Groups groups, First first) {
+  for (int n = 1; n <= NMAX; n++)
+    for (int al = 0; al < 4; al++)
+      for (int c = 0; c < n; c++) {
+        int holders = 0;
+        for (int k = 0; k < groups(n); k++) holders += first(k, al) <= c && c < first(k, al) + 4;
+        CHECK(holders == 1, "groups of %d cells al %d: cell %d in %d groups", n, al, c, holders);
+      }
 }

@@ -1,6 +1,6 @@
 """Host-compiler checks of the device headers in stretch_mujoco_amd/csrc: build a stand-alone check program with g++, run it, run it
 again under AddressSanitizer / UBSan where their runtime links, and compile a header on its own.  Plain helpers for
-tests/test_{point_cloud,height_map,occupancy,distance}_harness.py; nothing here is loaded into python."""
+tests/test_{point_cloud,height_map,occupancy,distance,navigation}_harness.py; nothing here is loaded into python."""
 import os
 import subprocess
 

@@ -77,8 +77,8 @@ struct HostPot {
 template <class F>
 static void store_groups(std::vector<int>& out, long e0, int ncell, int base_words, std::vector<int>& written, int* wide, F value) {
   const int al = (int)((base_words + e0) & 3);
-  for (int k = 0; k < smj_nav_groups(ncell); k++) {
-    const int first = smj_nav_group_first(k, al);
+  for (int k = 0; k < smj_grid_groups(ncell); k++) {
+    const int first = smj_grid_group_first(k, al);
     if (first >= ncell) continue;
     if (first >= 0 && first + 4 <= ncell) {
       CHECK(((base_words + e0 + first) & 3) == 0, "a whole group off its 16-byte boundary");
@@ -213,16 +213,7 @@ static void check_pieces() {
     CHECK(covered == len, "the runs cover %d of %d", covered, len);
   }
   CHECK(smj_nav_max_sweeps(256, 256) == 65536 && SMJ_NAV_LDS_CELLS >= 16384 && SMJ_NAV_MAX_CELLS == 65536, "bounds");
-  for (int n = 1; n <= 70; n++)
-    for (int al = 0; al < 4; al++) {
-      std::vector<int> seen(n, 0);
-      for (int k = 0; k < smj_nav_groups(n); k++)
-        for (int i = 0; i < 4; i++) {
-          const int c = smj_nav_group_first(k, al) + i;
-          if (c >= 0 && c < n) seen[c]++;
-        }
-      for (int v : seen) CHECK(v == 1, "groups of %d cells al %d", n, al);
-    }
+  check_store_groups<70>(smj_grid_groups, smj_grid_group_first);
   {   // the 3 x 3 case by hand: goal (0, 0), lethal (0, 1), neutral 1
     Map m = blank(3, 3, 253, 1);
     m.cost[1] = 254;

@@ -1,12 +1,17 @@
-"""The scene the GPU tests of the perception entries share (tests/test_gpu_{point_cloud,height_map,occupancy,distance}.py):
+"""The scene the GPU tests of the perception entries share (tests/test_gpu_{point_cloud,height_map,occupancy,distance,navigation}.py):
 stretch_scene, three envs driven apart, 200 steps.  Each test module keeps its own module-scoped fixture, which calls build() with
-its cameras and sensors and adds what only it needs."""
+its cameras and sensors (lidar_rig() for the lidar's entries), adds what only it needs and stops the simulator after its yield;
+bare_context() is the whole body of the `bare` fixtures.  Below those: the small helpers of the C calls, the guarded output buffers."""
 import ctypes
+import os
 
 import numpy as np
 import torch
 
+from conftest import ROOT
+
 B = 3
+DEV = "cuda:0"
 # per env: base x, y, yaw; lift; wrist pitch (down: the wrist camera sees the floor inside its 1 m limit); head pan
 POSES = [(0.0, 0.0, 0.0, 0.6, -0.8, 0.0), (-0.3, 0.2, 0.5, 0.3, -0.6, -0.8), (-0.5, -0.3, -0.7, 0.45, -0.7, 0.6)]
 
@@ -64,6 +69,60 @@ def build(cameras=(), sensors=(), pose_arm_and_head=False):
     r.base = int(sim.model["link_fused"][sim.names["body"].index("base_link")])
     r.cache = {}
     return r
+
+
+def lidar_rig():
+    """The rig with the lidar on and no camera."""
+    from stretch_mujoco_amd.enums import StretchSensors
+
+    return build(sensors=[StretchSensors.base_lidar])
+
+
+def bare_context():
+    """Fixture body: smj_create on the stretch_scene blob, B envs, NOTHING bound; .cache is the module's.  Destroyed at teardown."""
+    from stretch_mujoco_amd import lib
+
+    b = Rig()
+    b.L, b.ctx, b.cache = lib.load(), ctypes.c_void_p(), {}
+    with open(os.path.join(ROOT, "stretch_mujoco_amd", "models", "stretch_scene.smjb"), "rb") as f:
+        blob = f.read()
+    assert b.L.smj_create(blob, len(blob), B, 0, ctypes.byref(b.ctx)) == 0
+    yield b
+    torch.cuda.synchronize()
+    b.L.smj_destroy(b.ctx)
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream():
+    return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+
+
+def same(tag, got, want):
+    got = got.cpu().numpy()
+    assert np.array_equal(got, want), (tag, int((got != want).sum()), np.argwhere(got != want)[:5].tolist())
+
+
+def sentinels(ny, nx, fill=-7):
+    """A pair of int32 outputs [B, ny, nx] full of a value no entry writes there."""
+    return (torch.full((B, ny, nx), fill, dtype=torch.int32, device=DEV), torch.full((B, ny, nx), fill, dtype=torch.int32, device=DEV))
+
+
+class Guarded:
+    """An int32 output [B, ny, nx] as .view, `pad` words into a buffer of -12345 with 37 more behind it (pad 36: on a 16-byte boundary,
+    37: four bytes past one).  check(): the guards are untouched and the view equals `want`."""
+
+    def __init__(self, pad, ny, nx):
+        self.pad, self.cells = pad, B * ny * nx
+        self.big = torch.full((pad + self.cells + 37,), -12345, dtype=torch.int32, device=DEV)
+        self.view = self.big[pad:pad + self.cells].view(B, ny, nx)
+        assert self.view.data_ptr() % 16 == (4 * pad) % 16
+
+    def check(self, want):
+        assert (self.big[:self.pad] == -12345).all() and (self.big[self.pad + self.cells:] == -12345).all()
+        assert torch.equal(self.view, want)
 
 
 def frame_id(r, frame):

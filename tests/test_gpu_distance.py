@@ -10,7 +10,6 @@ Shapes (nx, ny): the smallest at which the kernel can go wrong -- single cells a
 (no 16-byte row alignment), 64 x 64, 131 x 127 (two strips of 66 and 65 columns), 4096 x 16 and 16 x 4096 (four strips each, the
 extremes of the cut), and 256 x 256 (four strips) once."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -18,49 +17,24 @@ import torch
 
 import distance_ref as ref
 import perception_rig
-from conftest import ROOT
+from perception_rig import B, DEV, Guarded, ptr as _ptr, same as _same, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-B = 3
-DEV = "cuda:0"
 SHAPES = [(1, 1), (7, 1), (1, 7), (16, 12), (61, 83), (64, 64), (131, 127), (4096, 16), (16, 4096)]
 NONE = 1 << 30
 
 
-class Bare:
-    pass
-
-
 @pytest.fixture(scope="module")
 def bare():
-    from stretch_mujoco_amd import lib
-
-    b = Bare()
-    b.L, b.lib = lib.load(), lib
-    with open(os.path.join(ROOT, "stretch_mujoco_amd", "models", "stretch_scene.smjb"), "rb") as f:
-        b.blob = f.read()
-    b.ctx = ctypes.c_void_p()
-    assert b.L.smj_create(b.blob, len(b.blob), B, 0, ctypes.byref(b.ctx)) == 0
-    b.cache = {}
-    yield b
-    torch.cuda.synchronize()
-    b.L.smj_destroy(b.ctx)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+    yield from perception_rig.bare_context()
 
 
 def _edt(b, hit, miss=None, min_hits=1, unknown=0, R=0, nearest=True, out=None, rc=0):
     """One call on [B, ny, nx] int32 device tensors; the outputs start as sentinels."""
     _, ny, nx = hit.shape
     if out is None:
-        out = (torch.full((B, ny, nx), -7, dtype=torch.int32, device=DEV), torch.full((B, ny, nx), -7, dtype=torch.int32, device=DEV))
+        out = perception_rig.sentinels(ny, nx)
     got = b.L.smj_occupancy_to_distance(b.ctx, _ptr(hit), _ptr(miss), nx, ny, min_hits, unknown, R, _ptr(out[0]), _ptr(out[1]) if nearest else None, _stream())
     assert got == rc, (got, b.L.smj_last_error(b.ctx))
     return out
@@ -99,11 +73,6 @@ def _reference(b, nx, ny):
         out = [ref.field_of_mask(m) for m in g]
         b.cache[key] = (g, np.stack([o[0] for o in out]), np.stack([o[1] for o in out]))
     return b.cache[key]
-
-
-def _same(tag, got, want):
-    got = got.cpu().numpy()
-    assert np.array_equal(got, want), (tag, int((got != want).sum()), np.argwhere(got != want)[:5].tolist())
 
 
 def test_strip_cut_of_the_shapes():
@@ -213,20 +182,16 @@ def test_nothing_outside_the_outputs_is_written_and_alignment_does_not_matter(ba
         assert want[0].data_ptr() % 16 == 0 and want[1].data_ptr() % 16 == 0
         results = []
         for (h, m), dpad, npad in (((hit, miss), pad, pad), ((hv, mv), pad, pad), ((hit, miss), pad, 36), ((hit, miss), 36, pad), ((hv, mv), 36, 36)):
-            dbig = torch.full((dpad + cells + pad,), -12345, dtype=torch.int32, device=DEV)
-            nbig = torch.full((npad + cells + pad,), -12345, dtype=torch.int32, device=DEV)
-            dv, nv = dbig[dpad:dpad + cells].view(B, ny, nx), nbig[npad:npad + cells].view(B, ny, nx)
-            assert dv.data_ptr() % 16 == (4 * dpad) % 16 and nv.data_ptr() % 16 == (4 * npad) % 16
-            _edt(b, h, m, unknown=unknown, R=R, out=(dv, nv))
-            results.append((dbig, nbig, dpad, npad))
+            dg, ng = Guarded(dpad, ny, nx), Guarded(npad, ny, nx)
+            _edt(b, h, m, unknown=unknown, R=R, out=(dg.view, ng.view))
+            results.append((dg, ng))
         torch.cuda.synchronize()
         wd, wn = ref.field(hit.cpu().numpy(), miss.cpu().numpy(), 1, bool(unknown), R)
         _same("aligned dist2", want[0], wd)
         _same("aligned nearest", want[1], wn)
-        for dbig, nbig, dpad, npad in results:
-            for big, p, w in ((dbig, dpad, want[0]), (nbig, npad, want[1])):
-                assert (big[:p] == -12345).all() and (big[p + cells:] == -12345).all()
-                assert torch.equal(big[p:p + cells].view(B, ny, nx), w)
+        for dg, ng in results:
+            dg.check(want[0])
+            ng.check(want[1])
     assert hbig[0] == -77 and (hbig[1 + cells:] == -77).all() and mbig[0] == -77 and (mbig[1 + cells:] == -77).all()
     assert torch.equal(hv, hit) and torch.equal(mv, miss)      # the inputs are unchanged
 
@@ -275,9 +240,7 @@ def test_error_codes_and_a_refused_call_writes_nothing(bare):
 @pytest.fixture(scope="module")
 def rig():
     """The rig of tests/test_gpu_occupancy.py: stretch_scene, three envs driven apart, 200 steps, the lidar on."""
-    from stretch_mujoco_amd.enums import StretchSensors
-
-    r = perception_rig.build(sensors=[StretchSensors.base_lidar])
+    r = perception_rig.lidar_rig()
     yield r
     r.sim.stop()
 

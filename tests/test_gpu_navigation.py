@@ -9,7 +9,6 @@ Shapes (nx, ny): the smallest at which the kernel can go wrong -- a single cell,
 16-byte row alignment), 128 x 128 (SMJ_NAV_LDS_CELLS = 16384 cells: the largest grid whose potential lives in LDS), 129 x 128 (the
 smallest one relaxed in potential_dev itself), 4096 x 4 and 4 x 4096 (16 lines per thread one way, the longest lines cut into 32 runs the other), and 256 x 256 once."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -17,43 +16,18 @@ import torch
 
 import navigation_ref as ref
 import perception_rig
-from conftest import ROOT
+from perception_rig import B, DEV, Guarded, ptr as _ptr, same as _same, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-B = 3
 G = 3
-DEV = "cuda:0"
 SHAPES = [(1, 1), (7, 1), (1, 7), (16, 12), (61, 83), (128, 128), (129, 128), (4096, 4), (4, 4096)]
 NONE = 1 << 30
 
 
-class Bare:
-    pass
-
-
 @pytest.fixture(scope="module")
 def bare():
-    from stretch_mujoco_amd import lib
-
-    b = Bare()
-    b.L, b.lib = lib.load(), lib
-    with open(os.path.join(ROOT, "stretch_mujoco_amd", "models", "stretch_scene.smjb"), "rb") as f:
-        b.blob = f.read()
-    b.ctx = ctypes.c_void_p()
-    assert b.L.smj_create(b.blob, len(b.blob), B, 0, ctypes.byref(b.ctx)) == 0
-    b.cache = {}
-    yield b
-    torch.cuda.synchronize()
-    b.L.smj_destroy(b.ctx)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+    yield from perception_rig.bare_context()
 
 
 def _nav(b, cost, goal, lethal=253, neutral=50, shape=None, nxt=True, out=None, rc=0):
@@ -61,7 +35,7 @@ def _nav(b, cost, goal, lethal=253, neutral=50, shape=None, nxt=True, out=None, 
     sentinels."""
     ny, nx = shape if cost is None else cost.shape[1:]
     if out is None:
-        out = (torch.full((B, ny, nx), -7, dtype=torch.int32, device=DEV), torch.full((B, ny, nx), -7, dtype=torch.int32, device=DEV))
+        out = perception_rig.sentinels(ny, nx)
     got = b.L.smj_costmap_to_navigation(b.ctx, _ptr(cost), _ptr(goal), goal.shape[1], nx, ny, lethal, neutral, _ptr(out[0]), _ptr(out[1]) if nxt else None,
                                         _stream())
     assert got == rc, (got, b.L.smj_last_error(b.ctx))
@@ -131,11 +105,6 @@ def _reference(b, nx, ny):
             want.append((p, ref.next_of(c, p, **kw)))
         b.cache[key] = (cases, want)
     return b.cache[key]
-
-
-def _same(tag, got, want):
-    got = got.cpu().numpy()
-    assert np.array_equal(got, want), (tag, int((got != want).sum()), np.argwhere(got != want)[:5].tolist())
 
 
 def _device_inputs(cases):
@@ -238,20 +207,16 @@ def test_nothing_outside_the_outputs_is_written_and_alignment_does_not_matter(ba
     results = []
     for (c, g), ppad, npad in (((cost, goal), pad, pad), ((cv, gv), pad, pad), ((cost, goal), pad, 36), ((cost, goal), 36, pad), ((cv, gv), 36, 36),
                                ((cv, gv), 38, 39)):
-        pbig = torch.full((ppad + cells + pad,), -12345, dtype=torch.int32, device=DEV)
-        nbig = torch.full((npad + cells + pad,), -12345, dtype=torch.int32, device=DEV)
-        pv, nv = pbig[ppad:ppad + cells].view(B, ny, nx), nbig[npad:npad + cells].view(B, ny, nx)
-        assert pv.data_ptr() % 16 == (4 * ppad) % 16 and nv.data_ptr() % 16 == (4 * npad) % 16
-        _nav(b, c, g, out=(pv, nv))
-        results.append((pbig, nbig, ppad, npad))
+        pg, ng = Guarded(ppad, ny, nx), Guarded(npad, ny, nx)
+        _nav(b, c, g, out=(pg.view, ng.view))
+        results.append((pg, ng))
     torch.cuda.synchronize()
     for e in range(B):
         _same("aligned potential", aligned[0][e], want[idx[pick[e][0]]][0])
         _same("aligned next", aligned[1][e], want[idx[pick[e][0]]][1])
-    for pbig, nbig, ppad, npad in results:
-        for big, p, w in ((pbig, ppad, aligned[0]), (nbig, npad, aligned[1])):
-            assert (big[:p] == -12345).all() and (big[p + cells:] == -12345).all()
-            assert torch.equal(big[p:p + cells].view(B, ny, nx), w)
+    for pg, ng in results:
+        pg.check(aligned[0])
+        ng.check(aligned[1])
     assert cbig[0] == 99 and (cbig[1 + cells:] == 99).all() and gbig[0] == -77 and (gbig[1 + B * G:] == -77).all()
     assert torch.equal(cv, cost) and torch.equal(gv, goal)      # the inputs are unchanged
 
@@ -303,9 +268,7 @@ def test_error_codes_and_a_refused_call_writes_nothing(bare):
 @pytest.fixture(scope="module")
 def rig():
     """The rig of tests/test_gpu_occupancy.py: stretch_scene, three envs driven apart, 200 steps, the lidar on."""
-    from stretch_mujoco_amd.enums import StretchSensors
-
-    r = perception_rig.build(sensors=[StretchSensors.base_lidar])
+    r = perception_rig.lidar_rig()
     yield r
     r.sim.stop()
 

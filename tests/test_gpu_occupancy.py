@@ -19,7 +19,7 @@ import torch
 
 import occupancy_ref as ref
 import perception_rig
-from perception_rig import B, f32, to32
+from perception_rig import B, Guarded, f32, to32
 from perception_rig import frame_id as _fid
 from point_cloud_ref import body_pose
 
@@ -33,9 +33,7 @@ LIMITS = (0.2, 9.5)
 
 @pytest.fixture(scope="module")
 def rig():
-    from stretch_mujoco_amd.enums import StretchSensors
-
-    r = perception_rig.build(sensors=[StretchSensors.base_lidar])
+    r = perception_rig.lidar_rig()
     sim = r.sim
     assert sim.nlidar == K
     r.scan = sim.lidar[:K].clone()                      # [K, B] batch-major, ld = B: what SMJ_SLOT_LIDAR holds
@@ -66,13 +64,9 @@ def _geometry(r, frame, xpose=None):
     return out
 
 
-def _new(r, nx, ny, fill=7):
-    return (torch.full((B, ny, nx), fill, dtype=torch.int32, device=r.sim.device), torch.full((B, ny, nx), fill, dtype=torch.int32, device=r.sim.device))
-
-
 def _occ(r, scan, frame, x0, y0, cell, nx, ny, r_min, r_max, clears=1, acc=0, out=None, miss=True, ctx=None, rc=0, ld=None):
     if out is None:
-        out = _new(r, nx, ny)
+        out = perception_rig.sentinels(ny, nx, 7)
     got = r.L.smj_lidar_to_occupancy(ctx or r.sim._ctx, ctypes.c_void_p(scan.data_ptr()), scan.stride(0) if ld is None else ld, frame, x0, y0, cell, nx, ny,
                                      r_min, r_max, clears, acc, ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()) if miss else None,
                                      r.sim._stream())
@@ -224,7 +218,7 @@ def test_invariants(rig):
                 assert int((t[0] + t[1]).max()) <= K and int(t[0].min()) >= 0 and int(t[1].min()) >= 0
             assert int((a[0] > 0).sum()) > 20 and int((a[1] > 0).sum()) > 500 and not torch.equal(a[0], b[0])
             # without a miss buffer the hits are the same and nothing else is touched; accumulating without one adds the hits
-            h_only = _new(r, nx, ny)
+            h_only = perception_rig.sentinels(ny, nx, 7)
             call(r.scan, out=h_only, miss=False)
             assert torch.equal(h_only[0], a[0]) and int((h_only[1] != 7).sum()) == 0
             call(other, out=h_only, miss=False, acc=1)
@@ -286,21 +280,17 @@ def test_nothing_outside_the_outputs_is_written_and_alignment_does_not_matter(ri
             grid = (f32(-nx * 0.05 / 2 + 0.013), f32(-ny * 0.05 / 2 - 0.013), f32(0.05), nx, ny, f32(0.2), f32(9.5))
             want = _occ(r, r.scan, _fid(r, frame), *grid)
             assert want[0].data_ptr() % 16 == 0 and want[1].data_ptr() % 16 == 0
-            cells, pad = B * nx * ny, 37      # 37 words = 148 bytes = 4 mod 16
+            pad = 37      # 37 words = 148 bytes = 4 mod 16
             results = []
             for scan, hpad, mpad in ((r.scan, pad, pad), (sview, pad, pad), (r.scan, pad, 36), (r.scan, 36, pad), (sview, 36, 36)):
-                hbig = torch.full((hpad + cells + pad,), -12345, dtype=torch.int32, device=dev)
-                mbig = torch.full((mpad + cells + pad,), -12345, dtype=torch.int32, device=dev)
-                hv, mv = hbig[hpad: hpad + cells].view(B, ny, nx), mbig[mpad: mpad + cells].view(B, ny, nx)
-                assert hv.data_ptr() % 16 == (4 * hpad) % 16 and mv.data_ptr() % 16 == (4 * mpad) % 16
-                _occ(r, scan, _fid(r, frame), *grid, out=(hv, mv))
-                results.append((hbig, mbig, hpad, mpad))
+                hg, mg = Guarded(hpad, ny, nx), Guarded(mpad, ny, nx)
+                _occ(r, scan, _fid(r, frame), *grid, out=(hg.view, mg.view))
+                results.append((hg, mg))
             torch.cuda.synchronize()
             assert int((want[1] > 0).sum()) > 0 and (int((want[0] > 0).sum()) > 0 or nx < 61)      # (nothing stands within 0.4 m of the robot)
-            for hbig, mbig, hpad, mpad in results:
-                for big, p, w in ((hbig, hpad, want[0]), (mbig, mpad, want[1])):
-                    assert (big[:p] == -12345).all() and (big[p + cells:] == -12345).all()
-                    assert torch.equal(big[p: p + cells].view(B, ny, nx), w)
+            for hg, mg in results:
+                hg.check(want[0])
+                mg.check(want[1])
     assert sbig[0] == -77.0 and (sbig[1 + K * B:] == -77.0).all() and torch.equal(sview, r.scan)
 
 

@@ -1,23 +1,15 @@
 """include/smj_navigation.h (the navigation-field entry; smj_distance.h includes it, smj_occupancy.h that one and smj.h that one) and
-the loader agree, as tests/test_distance_capi.py checks for smj_distance.h.  capi_check.header_and_loader_agree has a fixed list of
-export tuples, so its assertions are written out here with the new tuple added."""
-import os
+the loader agree, as tests/test_distance_capi.py checks for smj_distance.h."""
 import re
 
 import capi_check
-from conftest import ROOT
 from stretch_mujoco_amd import lib
 
 NAME, ENTRY = "smj_navigation.h", "smj_costmap_to_navigation"
 
 
 def test_header_and_loader_agree():
-    assert capi_check.declared(capi_check.header(NAME)) == sorted(lib.NAVIGATION_EXPORTS) == [ENTRY]
-    others = [n for n in sorted(os.listdir(os.path.join(ROOT, "include"))) if n != NAME]
-    assert ENTRY not in sum((capi_check.declared(capi_check.header(n)) for n in others), [])
-    old = [lib.EXPORTS, lib.POINT_EXPORTS, lib.HEIGHTMAP_EXPORTS, lib.OCCUPANCY_EXPORTS, lib.DISTANCE_EXPORTS, lib.BUILD_EXPORTS]
-    for group in old:
-        assert not set(group) & set(lib.NAVIGATION_EXPORTS), group
+    capi_check.header_and_loader_agree(NAME, lib.NAVIGATION_EXPORTS, ENTRY)
     text = capi_check.header(NAME)
     assert int(re.search(r"#define\s+SMJ_NAV_NONE\s+\(1 << (\d+)\)", text).group(1)) == 30 and lib.NAV_NONE == 1 << 30
     assert len(re.findall(r"^#define\s+SMJ_", text, flags=re.M)) == 2      # the include guard and SMJ_NAV_NONE

@@ -194,8 +194,9 @@ struct DevModel;
 struct DevState;
 struct ihipStream_t;
 struct SmjCaps { int nvp, nbp, nent, nefc, ncon, nvs, nsat; };   // nvs: dof columns of the variant's matrices (0: nvp); nsat: satellite capacity (0: a build without satellites)
-// return 0, a hipError_t, or SMJ_LAUNCH_REFUSED_SOLVER (the launcher's own guard: nothing was launched)
-typedef int (*SmjLaunch)(const DevModel& m, const DevState& s, int nsteps, unsigned read_flags, ihipStream_t* stream);
+// return 0, a hipError_t, or SMJ_LAUNCH_REFUSED_SOLVER (the launcher's own guard: nothing was launched).  The grid is the caller's
+// (smj_step_plan.h): s.pipe_total workgroups of the primary kernel, worker_wgs of the escalation worker (s.redo_worker; else ignored)
+typedef int (*SmjLaunch)(const DevModel& m, const DevState& s, int nsteps, unsigned read_flags, int worker_wgs, ihipStream_t* stream);
 #define SMJ_LAUNCH_REFUSED_SOLVER (-7001)   // its own value, not a HIP error code: a genuine hipErrorInvalidValue of a launch (a bad LDS size ...) must not be mistaken for it
 struct SmjBuildDesc {
   const char *tag, *family, *kernel, *worker;   // worker: the escalation worker kernel, or null

@@ -17,7 +17,7 @@
 #include "../../include/smj.h"
 #include "../../include/smj_build.h"
 #include "smj_kernels.h"
-#include "smj_variants.h"
+#include "smj_step_plan.h"
 #include "smj_model_load.h"
 #include "smj_bvh.h"
 #include "smj_meshlet.h"
@@ -47,30 +47,14 @@ struct smj_ctx {
   DevModel model_esc{};
   bool has_esc = false;
   int* redo = nullptr;
-  int escalate = 1;
+  SmjStepOptions opt;      // the host-side scheduling options (smj_step_plan.h)
   // launch order: per-env shader time of the last launch and the permutation sorted by it (DevState::order / cost)
   int* cost = nullptr;
   int* order = nullptr;
-  int balance = 1;
   int lidar_cull = 1;      // lidar: drop, per env, the geoms that cannot reach the scan plane (smj_render.h lidar_plane_*)
-  int balance_min_envs = 1024; // cost-ordered dispatch only above this many envs (option balance_min_envs)
-  // pipelined chunks (and with them the pollers) only above this many envs (option pipeline_min_envs).  Round 5: 511, was 1024 -- measured under
-  // random actions at 1024 envs: empty scene 5.16 -> 5.52 M, kitchen stand-in 3.97 -> 4.98 M, scene.xml 1.96 -> 2.37 M, the kitchen at Robocasa
-  // scale 0.73 -> 1.30 M (an env handed to the large build is finished beside the launch instead of after it); at 512 envs nothing but the
-  // last (0.56 -> 0.77 M); settled scenes pay 3-5 % for the chunks' state round trips at these sizes
-  int pipe_min_envs = 511;
-  int newton_two_waves = 3;   // Newton on the 16-satellite build: 1 = the two-wavefront kernel (smj_kernels_sat2.hip: the second wavefront takes the moving-moving pairs and the satellites' lane-serial stages), 0 = one wavefront per env
-  int pgs_two_waves = 1;   // PGS on the 16-satellite build: 1 = the two-wavefront kernel (smj_kernels_satp.hip), 0 = one wavefront per env
-  int balance_min = 1;   // steps per launch from which the cost-ordered dispatch is used (round 4: 1 -- a one-step launch is as long as its slowest round of workgroups; was 4)
-  int chunk = 0;               // steps per dispatch inside one smj_step (0: the whole launch at once; measured: no gain)
-  int pipeline_big = 1;        // pipelined dispatch for the two-envs-per-CU builds of the big variant too (option "pipeline_big")
-  int pipeline = 5;            // chunk length of the pipelined dispatch (DevState::pipe_len; 0 = one workgroup per env for the whole launch)
-  bool pollers_always = false; // option "pollers" < 0: send the pollers with every launch (tests)
   bool prof_warned = false;    // the one-time warning of smj_step: profiling slot bound, the PGS kernel launched has no counters
-  int lean_build = 1;          // option "lean_build": 1 = a call that qualifies (smj_variants.h smj_lean_eligible) runs the lean twin of the standard Newton build, 0 = always the general build
   const SmjBuildDesc* last_primary = nullptr;   // the primary build of the last smj_step (smj_last_build)
-  int pollers = 2;             // tall-variant workgroups that finish parked envs beside the standard kernel (0: the sweep does it all)
-  int* progress = nullptr;     // [B] progress, [B] done_steps, [SMJ_SCHED_WORDS] sched (DevState)
+  int* progress = nullptr;    // [B] progress, [B] done_steps, [SMJ_SCHED_WORDS] sched (DevState)
   size_t redo_cap = 0;         // entries the escalation list holds
   hipStream_t aux = nullptr;   // the pollers' stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -408,17 +392,8 @@ int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ct
   c->device = device;
   c->num_envs = num_envs;
   HIPCHK(c, hipSetDevice(device));
-  {
-    // The pipelined chunks (and the pollers beside them) lean on workgroups being dispatched in index order: an env's chunk k + 1
-    // waits -- bounded, 3 s -- for chunk k, which sits B workgroups earlier in the grid.  That holds on the gfx94x / gfx950
-    // command processors this was measured on; on any other architecture the default is the plain launch (one workgroup per env
-    // for the whole call).  smj_set_option("pipeline", k) overrides it either way.
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && strncmp(prop.gcnArchName, "gfx94", 5) != 0)) {
-      c->pipeline = 0;
-      c->pollers = 0;
-    }
-  }
+  hipDeviceProp_t prop;
+  smj_step_options_for_arch(c->opt, hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.gcnArchName : nullptr);
   DeviceUploader up{c};
   SmjCaps caps[SMJ_NVARIANTS];   // a variant's capacities are those of its Newton build
   for (int v = 0; v < SMJ_NVARIANTS; v++) caps[v] = smj_builds[smj_variants[v].newton]->caps;
@@ -438,7 +413,7 @@ int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ct
     c->has_esc = true;
     if (esc_caps->ncon > c->state.con_cap) c->state.con_cap = esc_caps->ncon;   // a handed-over step ends in the larger build
     void* d = nullptr;
-    c->redo_cap = 16 * (size_t)num_envs;   // a 50-step call is 10 chunks per env; longer calls re-allocate (smj_step)
+    c->redo_cap = smj_redo_initial_cap(num_envs);   // longer calls re-allocate (smj_step)
     HIPCHK(c, hipMalloc(&d, sizeof(int) * c->redo_cap));
     c->redo = (int*)d;   // freed in smj_destroy (it can be re-allocated by smj_step)
     HIPCHK(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
@@ -586,100 +561,80 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   if (read_flags & SMJ_READ_POSES) out.add(st.xpose, 12 * m.nbody_all, Y.xpose);
   st.stage = c->stage;
   st.lay = Y;
-  const bool esc = c->has_esc && c->escalate;   // standard -> tall, big38 / big50 -> big (has_esc: smj_create)
-  st.redo = esc ? c->redo : nullptr;
   st.cost = c->cost;
-  if (esc) {   // the escalation target runs with the same options
+  // what the call is, which builds it launches (the escalation model runs with the primary's options: one routing for both; the lean
+  // twin of the standard Newton build in its place when this call can execute none of what that twin leaves out) and how every one of
+  // them is launched (smj_step_plan.h).  The rest of this function carries the plan out: each `if` below tests one of its fields.
+  const SmjVariant& V = smj_variants[c->variant];
+  const SmjCallFacts facts{c->num_envs, nsteps, st.debug != nullptr, st.prof != nullptr, c->has_esc};
+  const SmjRoute route = smj_route_lean(smj_route(c->variant, c->model.solver, facts.prof_bound, c->opt.newton_two_waves, c->opt.pgs_two_waves, smj_builds),
+                                        smj_lean_facts(c->model, st, c->opt.lean_build), smj_builds[SMJ_B_step], &smj_build_lean);
+  const SmjStepPlan plan = smj_plan_step(V, route, c->opt, facts);
+  c->last_primary = route.primary;
+  if (plan.esc) {   // the escalation target runs with the same options
 #define X(name, field, type) c->model_esc.field = c->model.field;
     SMJ_SOLVER_OPTIONS(X)
 #undef X
   }
-  smj_launch_stage(in, c->stage, Y.stride, c->num_envs, st.ld, false, (hipStream_t)stream);
-  // Option `chunk` (default 0 = off; kept for experiments): the n steps go out as separate dispatches of `chunk` steps on the
-  // staged rows, each with a fresh longest-first order.  Measured: no gain -- a barrier per chunk keeps the tail's share of a
-  // dispatch what it was; the pipelined chunks below have no barrier.  Readout flags go with the last chunk only.
-  const int chunk = (c->chunk > 0 && !st.debug && !st.prof && c->num_envs > 1024) ? c->chunk : nsteps;
-  // Pipelined chunks (standard variant, batches that need more than one round of workgroups): see DevState::pipe_len
   hipStream_t sm = (hipStream_t)stream;
-  const SmjVariant& V = smj_variants[c->variant];
-  const int pipe_len = V.chunk_len(c->pipeline);
-  const bool pipe = (V.pipelines == SMJ_PIPE_ALWAYS || (V.pipelines == SMJ_PIPE_IF_BIG && c->pipeline_big)) && c->pipeline > 0 && chunk == nsteps && nsteps > pipe_len && !st.debug && !st.prof && c->num_envs > c->pipe_min_envs;
+  smj_launch_stage(in, c->stage, Y.stride, c->num_envs, st.ld, false, sm);
   st.progress = st.done_steps = st.sched = st.hot = nullptr;
-  if (esc || pipe) {
+  if (plan.clear_sched) {
     st.progress = c->progress;
     st.done_steps = c->progress + c->num_envs;
     st.sched = c->progress + 2 * (size_t)c->num_envs;
     st.hot = st.sched + SMJ_SCHED_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->progress, 0, sizeof(int) * (2 * (size_t)c->num_envs + SMJ_SCHED_WORDS), sm));
   }
-  st.pipe_len = 0;
+  if ((size_t)plan.redo_need > c->redo_cap) {   // the list grows, never shrinks
+    HIPCHK(c, hipDeviceSynchronize());
+    (void)hipFree(c->redo);
+    c->redo = nullptr;
+    c->redo_cap = (size_t)plan.redo_need;
+    void* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, sizeof(int) * c->redo_cap));
+    c->redo = (int*)d;
+  }
+  // -1 = entry not published yet: only the pollers read entries while the list grows (the sweep runs after the kernel, the count is final)
+  if (plan.mark_unpublished) HIPCHK(c, hipMemsetAsync(c->redo, 0xff, sizeof(int) * (size_t)plan.pipe_total, sm));
+  st.redo = plan.esc ? c->redo : nullptr;
+  st.redo_worker = 0;
+  st.pipe_len = plan.pipe_len;
+  st.pipe_total = plan.pipe_total;
   st.pollers = 0;
-  // which builds this call launches (the escalation model runs with the primary's options: one routing for both)
-  // (and the lean twin of the standard Newton build in its place when this call can execute none of what that twin leaves out)
-  const SmjLeanFacts lean_facts = smj_lean_facts(c->model, st, c->lean_build);
-  const SmjRoute route = smj_route_lean(smj_route(c->variant, c->model.solver, st.prof != nullptr, c->newton_two_waves, c->pgs_two_waves, smj_builds), lean_facts,
-                                        smj_builds[SMJ_B_step], &smj_build_lean);
-  c->last_primary = route.primary;
+  st.order = nullptr;
+  if (plan.ordered) {
+    smj_launch_order(c->cost, c->order, c->num_envs, sm);
+    st.order = c->order;
+  }
   int lrc = 0;
-  for (int done = 0; done < nsteps && !lrc; done += chunk) {
-    const int k = nsteps - done < chunk ? nsteps - done : chunk;
-    const unsigned fl = done + k >= nsteps ? read_flags : 0u;
-    st.redo_worker = 0;
-    st.order = nullptr;
-    st.pipe_len = pipe ? pipe_len : 0;
-    st.pipe_total = c->num_envs * (pipe ? (k + pipe_len - 1) / pipe_len : 1);
-    if (esc || pipe) HIPCHK(c, hipMemsetAsync(c->progress, 0, sizeof(int) * (2 * (size_t)c->num_envs + SMJ_SCHED_WORDS), sm));
-    if (esc) {
-      if ((size_t)st.pipe_total > c->redo_cap) {   // every workgroup of the standard launch can park its env once
-        HIPCHK(c, hipDeviceSynchronize());
-        (void)hipFree(c->redo);
-        c->redo = nullptr;
-        c->redo_cap = (size_t)st.pipe_total;
-        void* d = nullptr;
-        HIPCHK(c, hipMalloc(&d, sizeof(int) * c->redo_cap));
-        c->redo = (int*)d;
-        st.redo = c->redo;
-      }
-      // -1 = entry not published yet: only the pollers read entries while the list grows (the sweep runs after the kernel, the count is final)
-      if (pipe && c->pollers > 0) HIPCHK(c, hipMemsetAsync(c->redo, 0xff, sizeof(int) * (size_t)st.pipe_total, sm));
-    }
-    if (c->balance && k >= c->balance_min && c->num_envs > c->balance_min_envs) {
-      smj_launch_order(c->cost, c->order, c->num_envs, sm);
-      st.order = c->order;
-    }
-    // A second kernel resident beside the standard one costs a launch in which nobody escalates 5 % (measured: one poller or
-    // sixteen, any poll interval, any stream priority), and escalations are rare events (0-2 envs per 50-step launch of 4096
-    // under random actions, each worth milliseconds when left to the sweep): the pollers leave at once unless one of the last
-    // SMJ_HOT_LAUNCHES launches had an escalation (DevState::hot, kept on the device -- the host runs many launches ahead)
-    const bool poll = esc && pipe && c->pollers > 0 && route.poller;
-    if (poll) {
-      // pollers first, on their own stream, so that they are resident when the standard kernel fills the device; should they
-      // not be (nothing guarantees it), parked envs are given up to the sweep, as without pollers
-      DevState sp = st;
-      sp.redo_worker = 2;
-      const int np = V.poller_mult * c->pollers;
-      sp.pollers = c->pollers_always ? -np : np;
-      sp.order = nullptr;
-      HIPCHK(c, hipEventRecord(c->ev_fork, sm));
-      HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-      lrc = route.poller->launch(c->model_esc, sp, k, fl, c->aux);
-      HIPCHK(c, hipEventRecord(c->ev_join, c->aux));
-    }
-    // The primary builds exist once per solver (smj_step_impl.h newton()); smj_route has picked the one that carries this call's
-    // solver by what the builds say of themselves -- a launcher's refusal (its own guard) is an error here, not a question.
-    if (!lrc) lrc = route.primary->launch(c->model, st, k, fl, sm);
-    if (lrc == SMJ_LAUNCH_REFUSED_SOLVER) return fail(c, -2, "build `%s` does not carry solver %d (variant %s)", route.primary->tag, c->model.solver, V.name);
-    if (route.no_counters && !c->prof_warned) {   // (once: the caller asked for stage cycles and gets zeros -- say so instead of returning them silently)
-      c->prof_warned = true;
-      fprintf(stderr, "libsmj: the profiling slot is bound but the PGS kernel of this build has no cycle counters (build `make bigprof` and load it through SMJ_LIB_PATH); the counters stay zero\n");
-    }
-    if (poll) HIPCHK(c, hipStreamWaitEvent(sm, c->ev_join, 0));
-    if (!lrc && esc) {
-      // the sweep: whatever is left of the envs that ran out of constraint rows / contact slots (parked at the start of the
-      // offending step) is finished by the tall variant (160 rows / 48 contacts); an empty list returns at once
-      st.redo_worker = 1;
-      st.pipe_len = 0;
-      lrc = route.sweep->launch(c->model_esc, st, k, fl, sm);
-    }
+  if (plan.poll) {
+    // pollers first, on their own stream, so that they are resident when the standard kernel fills the device; should they
+    // not be (nothing guarantees it), parked envs are given up to the sweep, as without pollers
+    DevState sp = st;
+    sp.redo_worker = 2;
+    sp.pollers = plan.poller_arg;
+    sp.order = nullptr;
+    HIPCHK(c, hipEventRecord(c->ev_fork, sm));
+    HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
+    lrc = route.poller->launch(c->model_esc, sp, nsteps, read_flags, plan.poller_wgs, c->aux);
+    HIPCHK(c, hipEventRecord(c->ev_join, c->aux));
+  }
+  // The primary builds exist once per solver (smj_step_impl.h newton()); smj_route has picked the one that carries this call's
+  // solver by what the builds say of themselves -- a launcher's refusal (its own guard) is an error here, not a question.
+  if (!lrc) lrc = route.primary->launch(c->model, st, nsteps, read_flags, 0, sm);
+  if (lrc == SMJ_LAUNCH_REFUSED_SOLVER) return fail(c, -2, "build `%s` does not carry solver %d (variant %s)", route.primary->tag, c->model.solver, V.name);
+  if (route.no_counters && !c->prof_warned) {   // (once: the caller asked for stage cycles and gets zeros -- say so instead of returning them silently)
+    c->prof_warned = true;
+    fprintf(stderr, "libsmj: the profiling slot is bound but the PGS kernel of this build has no cycle counters (build `make bigprof` and load it through SMJ_LIB_PATH); the counters stay zero\n");
+  }
+  if (plan.poll) HIPCHK(c, hipStreamWaitEvent(sm, c->ev_join, 0));
+  if (!lrc && plan.sweep) {
+    // the sweep: whatever is left of the envs that ran out of constraint rows / contact slots (parked at the start of the
+    // offending step) is finished by the tall variant (160 rows / 48 contacts); an empty list returns at once
+    st.redo_worker = 1;
+    st.pipe_len = 0;
+    lrc = route.sweep->launch(c->model_esc, st, nsteps, read_flags, plan.sweep_wgs, sm);
   }
   if (lrc) return fail(c, -2, "step kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
   smj_launch_stage(out, c->stage, Y.stride, c->num_envs, st.ld, true, (hipStream_t)stream);
@@ -865,22 +820,7 @@ int smj_set_option(smj_ctx* c, const char* name, double v) {
   else if (!strcmp(name, "depth_raster")) c->render.raster = (int)v;            // 0: ray cast the meshes through their BVHs (the round-2 path)
   else if (!strcmp(name, "depth_raster_splits")) c->render.raster_splits = (int)(v < 1 ? 1 : v > 256 ? 256 : v);
   else if (!strcmp(name, "primary_rows")) m.row_limit = (int)v;   // the escalation variant keeps its full capacity (model_esc is not touched)
-  else if (!strcmp(name, "escalate")) c->escalate = (int)v;
-  else if (!strcmp(name, "lean_build")) c->lean_build = (int)v;   // 0: every call runs the general build (A/B runs, tests); what qualifies a call for the lean one: smj_variants.h
-  else if (!strcmp(name, "balance")) c->balance = (int)v;
-  else if (!strcmp(name, "balance_min")) c->balance_min = (int)v;
-  else if (!strcmp(name, "pgs_two_waves")) c->pgs_two_waves = (int)v;
-  else if (!strcmp(name, "newton_two_waves")) c->newton_two_waves = (int)v == 1 ? 3 : (int)v;   // 1 (or 3): both satellite builds; 0: neither; tools: 5 = the 16-satellite build only, 2 = the 32-satellite one only
-  else if (!strcmp(name, "chunk")) c->chunk = (int)v;
-  else if (!strcmp(name, "pipeline")) c->pipeline = (int)v;
-  else if (!strcmp(name, "pipeline_big")) c->pipeline_big = (int)v;
-  else if (!strcmp(name, "pipeline_min_envs")) c->pipe_min_envs = (int)v;
-  else if (!strcmp(name, "balance_min_envs")) c->balance_min_envs = (int)v;
-  else if (!strcmp(name, "pollers")) {   // n > 0: n pollers when a recent launch escalated; -n: n pollers with every launch; 0: none
-    c->pollers_always = v < 0;
-    const int n = (int)(v < 0 ? -v : v);
-    c->pollers = n > 256 ? 256 : n;
-  }
+  else if (smj_set_step_option(c->opt, name, v)) {}   // the scheduling options, by the list of smj_step_plan.h
   else if (!smj_set_solver_option(m, name, v)) return fail(c, -1, "unknown option '%s'", name);   // the solver options of DevModel, by the list smj_step copies onto the escalation model
   return 0;
 }

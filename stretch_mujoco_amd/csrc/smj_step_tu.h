@@ -7,6 +7,7 @@
 #endif
 #define SMJ_STEP_TU 1
 #include "smj_builds.h"
+#include "smj_step_plan.h"
 #include "smj_kernels.h"
 #include "smj_step_impl.h"
 
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(SMJ_WG_THREADS) void SMJ_WORKER_KERNEL(const DevMod
 }
 #endif
 
-int SMJ_LAUNCH_STEP(const DevModel& m_in, const DevState& s, int nsteps, unsigned read_flags, hipStream_t stream) {
+int SMJ_LAUNCH_STEP(const DevModel& m_in, const DevState& s, int nsteps, unsigned read_flags, int worker_wgs, hipStream_t stream) {
   // a build that carries one solver only (smj_step_impl.h newton()) refuses a launch for the other instead of running its own
 #if defined(SMJ_ONLY_NEWTON)
   if (m_in.solver != 2) return SMJ_LAUNCH_REFUSED_SOLVER;
@@ -205,13 +206,10 @@ int SMJ_LAUNCH_STEP(const DevModel& m_in, const DevState& s, int nsteps, unsigne
   if (m_in.solver == 2) return SMJ_LAUNCH_REFUSED_SOLVER;
 #endif
   DevModel m = m_in;
-  size_t lds = smj_lds_bytes(m.solver != 2);
-  // A PGS launch of a primary kernel that can hand steps over (DevState::redo) keeps to the rows whose A fits the struct
-  // (smj_pgs_rows_static) and asks for no dynamic LDS: the variant's Newton occupancy instead of one env per CU.
-  if (m.solver != 2 && s.redo && !s.redo_worker && lds > sizeof(Smem) && smj_pgs_rows_static() > 0) {
-    m.pgs_cap = smj_pgs_rows_static();
-    lds = sizeof(Smem);
-  }
+  // (a PGS launch that can hand steps over: static rows, no dynamic LDS -- smj_step_plan.h)
+  const SmjLdsChoice choice = smj_pgs_static_choice(m.solver, s.redo != nullptr, s.redo_worker, smj_lds_bytes(m.solver != 2), sizeof(Smem), smj_pgs_rows_static());
+  const size_t lds = choice.lds;
+  if (choice.pgs_cap) m.pgs_cap = choice.pgs_cap;
   static size_t lds_allowed_dev[64] = {};   // per device: the attribute belongs to the device's copy of the kernel
   int dev_now = 0;
   (void)hipGetDevice(&dev_now);
@@ -227,14 +225,11 @@ int SMJ_LAUNCH_STEP(const DevModel& m_in, const DevState& s, int nsteps, unsigne
   }
 #if defined(SMJ_WORKER_KERNEL)
   if (s.redo_worker) {
-    const unsigned wg = s.redo_worker == 2 ? (unsigned)(s.pollers < 0 ? -s.pollers : s.pollers) : (unsigned)(nsteps <= 2 ? (s.B < 64 ? s.B : 64) : s.B < 512 ? s.B : 512);   // sweep: two envs per CU fit (one under PGS); surplus workgroups find the list drained and leave (a one-step launch: 64 -- the empty sweep is pure launch cost there)
-    hipLaunchKernelGGL(SMJ_WORKER_KERNEL, dim3(wg), dim3(SMJ_WG_THREADS), lds, stream, m, s, nsteps, read_flags);
+    hipLaunchKernelGGL(SMJ_WORKER_KERNEL, dim3((unsigned)worker_wgs), dim3(SMJ_WG_THREADS), lds, stream, m, s, nsteps, read_flags);
     return 0;
   }
 #endif
-  unsigned grid = s.B;
-  if (s.pipe_len) grid = (unsigned)s.B * (unsigned)((nsteps + s.pipe_len - 1) / s.pipe_len);
-  hipLaunchKernelGGL(SMJ_STEP_KERNEL, dim3(grid), dim3(SMJ_WG_THREADS), lds, stream, m, s, nsteps, read_flags);
+  hipLaunchKernelGGL(SMJ_STEP_KERNEL, dim3((unsigned)s.pipe_total), dim3(SMJ_WG_THREADS), lds, stream, m, s, nsteps, read_flags);
   return 0;
 }
 

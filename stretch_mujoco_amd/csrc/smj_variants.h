@@ -1,6 +1,7 @@
 // THE TABLE OF CAPACITY VARIANTS (smj_ctx::variant, picked by smj_load_model from the model's dimensions) and the one function that
 // says which builds of smj_builds.h a step call launches.  Host code without HIP types apart from the launcher pointer inside a
-// descriptor: smj_capi.hip includes it, and tests/routing pins it on the CPU.
+// descriptor: smj_capi.hip includes it, and tests/routing pins it on the CPU.  Second of three headers: smj_builds.h (which builds
+// exist), this one (which of them a call launches: smj_route), smj_step_plan.h (how the call launches them: smj_plan_step).
 #pragma once
 #include "smj_builds.h"
 

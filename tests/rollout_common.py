@@ -542,18 +542,36 @@ class EmulBackend:
 
 
 class HipBackend:
-    """libsmj.so through StretchBatchSimulator (the C-ABI path)."""
+    """libsmj.so through StretchBatchSimulator (the C-ABI path).
 
-    def __init__(self, scene, B, solver=2):
+    counters=True (the default): the simulator's debug=True, which binds SMJ_SLOT_DEBUG AND SMJ_SLOT_PROF -- with the profiling slot bound
+    smj_route sends the standard variant to build `prof` and keeps the satellite variants on their one-wavefront Newton builds.
+    counters=False: the debug dump alone (download() needs it), PROF unbound: the product builds `step` / `pgs` / `sat2` / `sat32n` run.
+    last_build(): the tag of the primary build of the last step call; builds_seen: every tag a step() of this backend has reported."""
+
+    def __init__(self, scene, B, solver=2, counters=True):
+        import ctypes
+
         import torch
 
         from stretch_mujoco_amd import StretchBatchSimulator
+        from stretch_mujoco_amd import lib as _lib
 
         self.torch = torch
-        self.sim = StretchBatchSimulator(num_envs=B, device="cuda:0", scene=scene, solver={0: "pgs", 2: "newton"}[solver], debug=True)
+        self.sim = StretchBatchSimulator(num_envs=B, device="cuda:0", scene=scene, solver={0: "pgs", 2: "newton"}[solver], debug=bool(counters))
         self.sim.start(home=False)
+        if not counters:
+            s = self.sim
+            dims = (ctypes.c_int * 16)()
+            _lib.check(s._L, s._ctx, s._L.smj_dims(s._ctx, dims), "smj_dims")
+            s.debug = torch.zeros(dims[_lib.DIM["DEBUG_FLOATS"]], B, dtype=torch.float32, device=s.device)
+            _lib.check(s._L, s._ctx, s._L.smj_bind(s._ctx, _lib.SLOT["DEBUG"], ctypes.c_void_p(s.debug.data_ptr()), B), "smj_bind(DEBUG)")
+        self.builds_seen = set()
         self.sim.set_option("pgs_dual_warmstart", 0)   # MuJoCo's own warm start, as the unmodified oracle's; tests of the default (1) set it, on both sides
         self.D, self.nvp, self.ncon_max = self.sim.debug_layout, self.sim.nv_max, self.sim.ncon_max
+
+    def last_build(self):
+        return self.sim._L.smj_last_build(self.sim._ctx).decode()
 
     def _put(self, dst, a):
         dst.copy_(self.torch.as_tensor(np.ascontiguousarray(a), dtype=self.torch.float32).to(dst.device))
@@ -570,6 +588,7 @@ class HipBackend:
 
     def step(self, n):
         self.sim.step(n)
+        self.builds_seen.add(self.last_build())
 
     def download(self):
         s = self.sim

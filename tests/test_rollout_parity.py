@@ -120,6 +120,42 @@ def _check_events(rel, events):
     assert len(gross) <= 0.005 * len(rel) + 2
 
 
+def _check_pgs(rel, events, tag=""):
+    """The bounds of a state-synchronised PGS run with MuJoCo's QCQP iteration and MuJoCo's warm start on both sides, robot dofs and object
+    dofs each on their own scale -- those of test_satellites.test_gpu_pgs_satellite_build_state_synchronised with dual = 0, which the dense
+    builds share: 100 sweeps on nearly every step, neither side converged, the remainder carries the sweeps' rounding.  Object dofs on each
+    side's own narrowphase sit at p50 1.5e-3 .. 1.8e-3 (3e-5 on the kernel's contact list), hence not OBJ_TOL."""
+    S = rc.state_synchronised
+    ro, ob, sr, so, c = S.rel_robot, S.rel_obj, S.same_robot, S.same_obj, S.contacts
+    pc = lambda a: f"p50 {np.percentile(a, 50):.1e} p90 {np.percentile(a, 90):.1e} p99 {np.percentile(a, 99):.1e} max {a.max():.1e}"
+    print(f"\n[{tag}PGS] {len(rel)} env-steps, rel qacc: robot {pc(ro)}; objects, own narrowphase {pc(ob)}; on the kernel's contact list: robot {pc(sr)}; objects {pc(so)}; "
+          f"sweeps per step {S.iters[:, 0].mean():.1f} (oracle {S.iters[:, 1].mean():.1f}); events {len(events)}; contacts {c['n']}, steps with differing pair lists {c['mismatched_steps']}")
+    for ev in rc.gross_events(events):
+        print("   ", ev)
+    assert np.percentile(ro, 50) < 5e-4 and np.percentile(ro, 90) < 3e-3 and np.percentile(ro, 99) < 5e-2, pc(ro)
+    assert np.percentile(so, 50) < 5e-3, pc(so)
+    assert np.percentile(ob, 99) < 5e-2 and np.percentile(so, 99) < 5e-2, (pc(ob), pc(so))
+    assert c["mismatched_steps"] <= 0.005 * len(rel) + 1
+    assert all(ev["explained"] and ev["flags"] == 0 for ev in events), [ev for ev in events if not ev["explained"]]
+
+
+@pytest.mark.parametrize("scene,variant", [("stretch_kitchen_standin", "mid"), ("stretch_scene", None), ("stretch_kitchen4", None)])
+def test_emul_pgs_dense_builds_state_synchronised(scene, variant):
+    """PGS at the capacities of the dense builds beyond the standard one -- 128 rows / 44 contacts (`mid`, named: the emulator's default for
+    the stand-in is mid's hand-over target), 38 and 50 dof columns -- through the lane emulator: 2 envs x 100 steps of the bench workload,
+    the oracle's state uploaded before every step, MuJoCo's QCQP iteration and warm start on both sides; a step that runs out of rows is
+    finished by the build the device hands it to (emul.escalation).  The CPU twin of the PGS rows of tests/build_matrix.py.
+    Measured (robot p50 / p90 / p99; objects p99 own narrowphase / kernel's contact list), 0 events, 0 differing pair lists:
+    stand-in 7.1e-5 / 2.1e-4 / 4.4e-4; scene 8.9e-5 / 2.6e-4 / 4.2e-3, 3.0e-3 / 3.8e-4; kitchen4 7.6e-5 / 2.2e-4 / 5.5e-4, 2.2e-3 / 6.0e-5."""
+    blob, model = _blob(scene)
+    be = rc.EmulBackend(blob, 2, solver=0, variant=variant)
+    assert be.e.variant == (variant or {"stretch_scene": "big38", "stretch_kitchen4": "big50"}[scene])
+    be.e.set_option("qcqp_exact", 1)
+    rel, events = rc.state_synchronised(be, blob, model, 2, 2, seed=5, solver=0, twin=_keeps_manifolds(model))
+    assert int(be.e.info[3].max()) == 0
+    _check_pgs(rel, events, f"emulator {scene}, ")
+
+
 @pytest.mark.parametrize("scene", SCENES)
 def test_emul_random_ctrl_free_running(scene):
     blob, model = _blob(scene)

@@ -136,8 +136,8 @@ struct DevModel {
   const int* k_grid_adr;  // [cells + 1]
   const int* k_grid_list; // static-geom indices, cell after cell
   const int* k_sg_cell;   // [nsgeom][6] cell range of the geom (lo xyz, hi xyz)
-  const float* k_sg_bound;   // [nsgeom][8] world AABB of the geom's oriented box: lo xyz, pad, hi xyz, pad
-  const float* k_sgw;        // [nsgeom][32] the geom in the world frame, in the order of the collision cache's arrays: pos 3, mat 9, box centre 3, half sizes 3, MPR centre 3, size 3, meta (bits)
+  const float* k_sg_bound;   // [nsgeom][SMJ_SGB_STRIDE] world AABB of the geom's oriented box: lo xyz, pad, hi xyz, pad
+  const float* k_sgw;        // [nsgeom][SMJ_SGW_STRIDE] the geom in the world frame, in the order of the collision cache's arrays: pos 3, mat 9, box centre 3, half sizes 3, MPR centre 3, size 3, meta (bits)
 #define X(n) const int* n;
   SMJ_MODEL_I32(X)
 #undef X
@@ -164,10 +164,29 @@ enum { SMJ_CP_PAIR = 0, SMJ_CP_G1, SMJ_CP_G2, SMJ_CP_S1, SMJ_CP_S2, SMJ_CP_MARGI
 // both joints; limit: range bound of the side, margin), equality polynomial, diagonal approximation, friction loss, solref, solimp
 enum { SMJ_RR_TYPE = 0, SMJ_RR_ID, SMJ_RR_D1, SMJ_RR_D2, SMJ_RR_Q1, SMJ_RR_Q2, SMJ_RR_V1, SMJ_RR_V2, SMJ_RR_DATA = 8, SMJ_RR_DIAG = 13,
        SMJ_RR_FLOSS = 14, SMJ_RR_SOLREF = 15, SMJ_RR_SOLIMP = 17, SMJ_RR_SAT = 22 /* satellite owning the row's dof, or -1 */, SMJ_RR_SDOF = 23 /* its dof inside the satellite */, SMJ_RR_STRIDE = 24 };
-// per-lane stage record: KinTab 36 words, BodyTab 24, DofTab 16, EntryTab 7 arrays of `nent` slots (padded to 4 words), ActTab 28
-constexpr int smj_lr_act(int nent) { return 76 + ((7 * nent + 3) & ~3); }
-constexpr int smj_lr_stride(int nent) { return smj_lr_act(nent) + 28; }
-enum { SMJ_LR_KIN = 0, SMJ_LR_BODY = 36, SMJ_LR_DOF = 60, SMJ_LR_ENT = 76, SMJ_LR_ACT = smj_lr_act(NENT), SMJ_LR_STRIDE = smj_lr_stride(NENT) };
+// per-lane stage record: five sub-records, KinTab 36 words, BodyTab 24, DofTab 16, EntryTab 7 arrays of `nent` slots (padded to 4
+// words), ActTab 28.  Written by smj_build_lanerec (smj_model_load.h), read back by the load(KinTab&) .. load(ActTab&) of
+// smj_step_impl.h: for each sub-record the word offset of every field inside it, and the words its loader reads (_WORDS).
+enum { SMJ_KIN_PARENT = 0, SMJ_KIN_LEVEL = 1, SMJ_KIN_JUMP = 2 /* [6] */, SMJ_KIN_POS = 8, SMJ_KIN_QUAT = 11,
+       SMJ_KIN_JTYPE = 15 /* the body's (<= 2) joints: type, qpos / dof address, qpos0, [2] each */, SMJ_KIN_JQADR = 17, SMJ_KIN_JDADR = 19, SMJ_KIN_JQ0 = 21,
+       SMJ_KIN_JAXIS = 23 /* [2][3], read as [6] */, SMJ_KIN_JPOS = 29 /* likewise */, SMJ_KIN_WORDS = 35 };
+enum { SMJ_BODY_ROOT = 0, SMJ_BODY_SUBSIZE, SMJ_BODY_PARENT, SMJ_BODY_DOFADR, SMJ_BODY_DOFNUM, SMJ_BODY_JUMP = 5 /* [6] */, SMJ_BODY_DOFMASK_LO = 11,
+       SMJ_BODY_DOFMASK_HI = 12, SMJ_BODY_INL = 13 /* inertia_local[10] */, SMJ_BODY_WORDS = 23 };
+enum { SMJ_DOF_BODY = 0, SMJ_DOF_JTYPE, SMJ_DOF_QADR, SMJ_DOF_FIRST, SMJ_DOF_BSUB, SMJ_DOF_VELMASK_LO = 5, SMJ_DOF_VELMASK_HI = 6, SMJ_DOF_DAMP = 7,
+       SMJ_DOF_STIFF = 8, SMJ_DOF_SPRING = 9, SMJ_DOF_ACT = 10 /* [2] */, SMJ_DOF_ACTMOM = 12 /* [2] */, SMJ_DOF_WORDS = 14 };
+// (entry arrays, in this order, `nent` slots each; the last four are read by the implicit integrator only)
+enum { SMJ_ENT_I = 0, SMJ_ENT_J, SMJ_ENT_ARM, SMJ_ENT_LACT, SMJ_ENT_DAMP, SMJ_ENT_DCOEF, SMJ_ENT_LCOEF, SMJ_ENT_ARRAYS = 7 };
+enum { SMJ_ACT_DOF = 0 /* [4] */, SMJ_ACT_QADR = 4 /* [4] */, SMJ_ACT_MOM = 8 /* [4] */,
+       SMJ_ACT_PRM = 12 /* [8], read as one array: */, SMJ_ACT_GAIN = SMJ_ACT_PRM, SMJ_ACT_BIAS = 13 /* [3] */, SMJ_ACT_CTRLRANGE = 16 /* [2] */, SMJ_ACT_FORCERANGE = 18 /* [2] */,
+       SMJ_ACT_FLAGS = 20, SMJ_ACT_GC_BODY = 21, SMJ_ACT_GC_MLO = 22, SMJ_ACT_GC_MHI = 23, SMJ_ACT_GC_MASS = 24, SMJ_ACT_GC_POS = 25 /* [3] */, SMJ_ACT_WORDS = 28 };
+enum { SMJ_LR_KIN = 0, SMJ_LR_BODY = 36, SMJ_LR_DOF = 60, SMJ_LR_ENT = 76 };
+constexpr int smj_lr_act(int nent) { return SMJ_LR_ENT + ((SMJ_ENT_ARRAYS * nent + 3) & ~3); }
+constexpr int smj_lr_stride(int nent) { return smj_lr_act(nent) + SMJ_ACT_WORDS; }
+enum { SMJ_LR_ACT = smj_lr_act(NENT), SMJ_LR_STRIDE = smj_lr_stride(NENT) };
+static_assert(SMJ_LR_KIN + SMJ_KIN_WORDS <= SMJ_LR_BODY && SMJ_LR_BODY + SMJ_BODY_WORDS <= SMJ_LR_DOF && SMJ_LR_DOF + SMJ_DOF_WORDS <= SMJ_LR_ENT &&
+              SMJ_LR_ENT + SMJ_ENT_ARRAYS * NENT <= SMJ_LR_ACT && SMJ_LR_ACT + SMJ_ACT_WORDS <= SMJ_LR_STRIDE, "lane record: a sub-record ends before the next one starts");
+static_assert((SMJ_LR_KIN | SMJ_LR_BODY | SMJ_LR_DOF | SMJ_LR_ENT | SMJ_LR_ACT | SMJ_LR_STRIDE | smj_lr_act(5) | smj_lr_act(8) | smj_lr_stride(5) | smj_lr_stride(8)) % 4 == 0, "lane record: every sub-record starts on 16 bytes (the loaders' __builtin_assume_aligned)");
+static_assert(SMJ_LR_BODY == 36 && SMJ_LR_DOF == 60 && SMJ_LR_ENT == 76 && smj_lr_act(5) == 112 && smj_lr_stride(5) == 140 && smj_lr_act(8) == 132 && smj_lr_stride(8) == 160, "lane record: the offsets every blob was loaded with");
 // plane-pair record: pair, geom1 (the plane), geom2, their bodies, geom2 type, margin, geom2 bounding radius / centre,
 // local frames of both geoms, geom2 size, then the contact parameters of the pair
 enum { SMJ_PP_PAIR = 0, SMJ_PP_G1, SMJ_PP_G2, SMJ_PP_B1, SMJ_PP_B2, SMJ_PP_T2, SMJ_PP_MARGIN, SMJ_PP_RBOUND2, SMJ_PP_BCEN2 = 8,
@@ -183,7 +202,14 @@ enum { SMJ_CG_GEOM = 0, SMJ_CG_BODY, SMJ_CG_META, SMJ_CG_POS = 3, SMJ_CG_MAT = 6
 enum { SMJ_SR_BODY = 0, SMJ_SR_JTYPE, SMJ_SR_QADR, SMJ_SR_DADR, SMJ_SR_NDOF, SMJ_SR_JNT, SMJ_SR_F = 8,
        SMJ_SR_POS = SMJ_SR_F + 0, SMJ_SR_QUAT = SMJ_SR_F + 3, SMJ_SR_JPOS = SMJ_SR_F + 7, SMJ_SR_JAXIS = SMJ_SR_F + 10, SMJ_SR_Q0 = SMJ_SR_F + 13,
        SMJ_SR_INL = SMJ_SR_F + 14, SMJ_SR_ARM = SMJ_SR_F + 24, SMJ_SR_DAMP = SMJ_SR_F + 30, SMJ_SR_STIFF = SMJ_SR_F + 36, SMJ_SR_SPRING = SMJ_SR_F + 37,
-       SMJ_SR_GCMASS = SMJ_SR_F + 38, SMJ_SR_GCIPOS = SMJ_SR_F + 39, SMJ_SR_STRIDE = 52 };
+       SMJ_SR_GCMASS = SMJ_SR_F + 38, SMJ_SR_GCIPOS = SMJ_SR_F + 39, SMJ_SR_STRIDE = 52,
+       // the blob's k_sat_i [nsat][8] ints and k_sat_f [nsat][44] doubles, which the record holds one after the other
+       SMJ_SAT_I_STRIDE = SMJ_SR_F, SMJ_SAT_F_STRIDE = SMJ_SR_STRIDE - SMJ_SR_F };
+// static geom in the world frame (k_sgw, floats), in the order of the collision cache's arrays: frame, bounding-box centre and half
+// sizes, MPR interior point, geom size, packed type|hull count|hull address (bits; SMJ_CG_META) -- and its world AABB (k_sg_bound)
+enum { SMJ_SGW_POS = 0, SMJ_SGW_MAT = 3, SMJ_SGW_CEN = 12, SMJ_SGW_HALF = 15, SMJ_SGW_CCEN = 18, SMJ_SGW_SIZE = 21, SMJ_SGW_META = 24, SMJ_SGW_WORDS = 25,
+       SMJ_SGW_STRIDE = 32 };
+enum { SMJ_SGB_LO = 0, SMJ_SGB_HI = 4, SMJ_SGB_STRIDE = 8 };
 // layout of one env's staging row (4-byte words); a function of the variant's capacities, so that host code compiled once
 // (smj_capi.hip) can address the rows of either kernel variant
 struct SmjStageLayout {

@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <math.h>
 #include <string.h>
 
@@ -98,210 +99,238 @@ struct SmjBlob {
   }
 };
 
+// The blob's tables on the host, by name, as the record builders read them: an index past a table's end reads 0.
+struct SmjHostTables {
+  std::map<std::string, std::vector<int>> i;
+  std::map<std::string, std::vector<float>> f;
+  int gi(const char* n, size_t k) { const std::vector<int>& v = i[n]; return k < v.size() ? v[k] : 0; }
+  float gf(const char* n, size_t k) { const std::vector<float>& v = f[n]; return k < v.size() ? v[k] : 0.f; }
+  static int fb(float v) { int b; memcpy(&b, &v, 4); return b; }   // a float's bit pattern: how the records hold floats
+};
+
 // Host restatement of what the kernel's stage-table loaders (smj_step_impl.h: KinTab, BodyTab, DofTab, EntryTab, ActTab)
-// used to gather per lane from the individual tables, one record per lane.
-// capacities of a kernel variant (smj_model.h): the loader builds its records for the variant that will run
-static inline std::vector<int> smj_build_lanerec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
-                                                 std::map<std::string, std::vector<float>>& F, int nent) {
+// used to gather per lane from the individual tables, one record per lane; the positions are the SMJ_KIN_* .. SMJ_ACT_* of smj_model.h.
+// nent: capacity of a kernel variant (smj_model.h) -- the loader builds its records for the variant that will run
+static inline std::vector<int> smj_build_lanerec(const DevModel& m, SmjHostTables& T, int nent) {
   const int LR_ACT = smj_lr_act(nent), LR_STRIDE = smj_lr_stride(nent);
   std::vector<int> rec(64 * LR_STRIDE, 0);
-  auto fb = [](float v) { int b; memcpy(&b, &v, 4); return b; };
-  auto gi = [&](const char* n, size_t k) { const std::vector<int>& v = I[n]; return k < v.size() ? v[k] : 0; };
-  auto gf = [&](const char* n, size_t k) { const std::vector<float>& v = F[n]; return k < v.size() ? v[k] : 0.f; };
   const int nb = m.nbody, nv = m.nv, nu = m.nu;
   for (int L = 0; L < 64; L++) {
     int* r = rec.data() + L * LR_STRIDE;
     {  // KinTab: parent, level, jump[6], pos[3], quat[4], jtype[2], jqadr[2], jdadr[2], jq0[2], jaxis[6], jpos[6]
       int* k = r + SMJ_LR_KIN;
       const int b = L < nb ? L : 0;
-      k[0] = gi("body_parentid", b); k[1] = L < nb ? gi("k_body_level", b) : -1;
-      for (int q = 0; q < 6; q++) k[2 + q] = (q < m.njump && L > 0 && L < nb) ? gi("k_body_jump", q * nb + b) : 0;
-      for (int q = 0; q < 3; q++) k[8 + q] = fb(gf("body_pos", 3 * b + q));
-      for (int q = 0; q < 4; q++) k[11 + q] = fb(gf("body_quat", 4 * b + q));
-      const int jn = gi("body_jntnum", b), ja = gi("body_jntadr", b);
+      k[SMJ_KIN_PARENT] = T.gi("body_parentid", b); k[SMJ_KIN_LEVEL] = L < nb ? T.gi("k_body_level", b) : -1;
+      for (int q = 0; q < 6; q++) k[SMJ_KIN_JUMP + q] = (q < m.njump && L > 0 && L < nb) ? T.gi("k_body_jump", q * nb + b) : 0;
+      for (int q = 0; q < 3; q++) k[SMJ_KIN_POS + q] = T.fb(T.gf("body_pos", 3 * b + q));
+      for (int q = 0; q < 4; q++) k[SMJ_KIN_QUAT + q] = T.fb(T.gf("body_quat", 4 * b + q));
+      const int jn = T.gi("body_jntnum", b), ja = T.gi("body_jntadr", b);
       for (int u = 0; u < 2; u++) {
-        const int jj = (L < nb && u < jn) ? ja + u : -1, jx = jj >= 0 ? jj : 0, qa = gi("jnt_qposadr", jx);
-        k[15 + u] = jj >= 0 ? gi("jnt_type", jx) : -1; k[17 + u] = qa; k[19 + u] = gi("jnt_dofadr", jx); k[21 + u] = fb(gf("qpos0", qa));
-        for (int q = 0; q < 3; q++) { k[23 + 3 * u + q] = fb(gf("jnt_axis", 3 * jx + q)); k[29 + 3 * u + q] = fb(gf("jnt_pos", 3 * jx + q)); }
+        const int jj = (L < nb && u < jn) ? ja + u : -1, jx = jj >= 0 ? jj : 0, qa = T.gi("jnt_qposadr", jx);
+        k[SMJ_KIN_JTYPE + u] = jj >= 0 ? T.gi("jnt_type", jx) : -1; k[SMJ_KIN_JQADR + u] = qa; k[SMJ_KIN_JDADR + u] = T.gi("jnt_dofadr", jx); k[SMJ_KIN_JQ0 + u] = T.fb(T.gf("qpos0", qa));
+        for (int q = 0; q < 3; q++) { k[SMJ_KIN_JAXIS + 3 * u + q] = T.fb(T.gf("jnt_axis", 3 * jx + q)); k[SMJ_KIN_JPOS + 3 * u + q] = T.fb(T.gf("jnt_pos", 3 * jx + q)); }
       }
     }
     {  // BodyTab: root, subsize, parent, dofadr, dofnum, jump[6], dofmask lo, hi, inertia_local[10]
       int* k = r + SMJ_LR_BODY;
       const int b = L < nb ? L : 0;
-      k[0] = gi("body_rootid", b); k[1] = gi("k_body_subtreesize", b); k[2] = gi("body_parentid", b); k[3] = gi("body_dofadr", b);
-      k[4] = L < nb ? gi("body_dofnum", b) : 0;
-      for (int q = 0; q < 6; q++) k[5 + q] = (q < m.njump && L > 0 && L < nb) ? gi("k_body_jump", q * nb + b) : 0;
-      k[11] = gi("k_body_dofmask_lo", b); k[12] = gi("k_body_dofmask_hi", b);
-      for (int q = 0; q < 10; q++) k[13 + q] = fb(gf("k_body_inertia_local", 10 * b + q));
+      k[SMJ_BODY_ROOT] = T.gi("body_rootid", b); k[SMJ_BODY_SUBSIZE] = T.gi("k_body_subtreesize", b); k[SMJ_BODY_PARENT] = T.gi("body_parentid", b);
+      k[SMJ_BODY_DOFADR] = T.gi("body_dofadr", b); k[SMJ_BODY_DOFNUM] = L < nb ? T.gi("body_dofnum", b) : 0;
+      for (int q = 0; q < 6; q++) k[SMJ_BODY_JUMP + q] = (q < m.njump && L > 0 && L < nb) ? T.gi("k_body_jump", q * nb + b) : 0;
+      k[SMJ_BODY_DOFMASK_LO] = T.gi("k_body_dofmask_lo", b); k[SMJ_BODY_DOFMASK_HI] = T.gi("k_body_dofmask_hi", b);
+      for (int q = 0; q < 10; q++) k[SMJ_BODY_INL + q] = T.fb(T.gf("k_body_inertia_local", 10 * b + q));
     }
     {  // DofTab: body, jtype, qadr, first, bsub, velmask lo, hi, damp, stiff, spring, act[2], actmom[2]
       int* k = r + SMJ_LR_DOF;
-      const int d = L < nv ? L : 0, j = gi("dof_jntid", d), db = gi("dof_bodyid", d), jt = gi("jnt_type", j);
-      k[0] = db; k[1] = jt; k[2] = gi("k_dof_qposadr", d); k[3] = gi("jnt_dofadr", j); k[4] = gi("k_body_subtreesize", db);
-      k[5] = gi("k_dof_velmask_lo", d); k[6] = gi("k_dof_velmask_hi", d);
-      k[7] = fb(gf("dof_damping", d));
-      k[8] = fb(jt == 0 ? 0.f : gf("jnt_stiffness", j));
-      k[9] = fb(jt == 0 ? 0.f : gf("qpos_spring", gi("jnt_qposadr", j)));
-      for (int u = 0; u < 2; u++) { k[10 + u] = gi("k_dof_act", 2 * d + u); k[12 + u] = fb(gf("k_dof_actmom", 2 * d + u)); }
+      const int d = L < nv ? L : 0, j = T.gi("dof_jntid", d), db = T.gi("dof_bodyid", d), jt = T.gi("jnt_type", j);
+      k[SMJ_DOF_BODY] = db; k[SMJ_DOF_JTYPE] = jt; k[SMJ_DOF_QADR] = T.gi("k_dof_qposadr", d); k[SMJ_DOF_FIRST] = T.gi("jnt_dofadr", j);
+      k[SMJ_DOF_BSUB] = T.gi("k_body_subtreesize", db); k[SMJ_DOF_VELMASK_LO] = T.gi("k_dof_velmask_lo", d); k[SMJ_DOF_VELMASK_HI] = T.gi("k_dof_velmask_hi", d);
+      k[SMJ_DOF_DAMP] = T.fb(T.gf("dof_damping", d));
+      k[SMJ_DOF_STIFF] = T.fb(jt == 0 ? 0.f : T.gf("jnt_stiffness", j));
+      k[SMJ_DOF_SPRING] = T.fb(jt == 0 ? 0.f : T.gf("qpos_spring", T.gi("jnt_qposadr", j)));
+      for (int u = 0; u < 2; u++) { k[SMJ_DOF_ACT + u] = T.gi("k_dof_act", 2 * d + u); k[SMJ_DOF_ACTMOM + u] = T.fb(T.gf("k_dof_actmom", 2 * d + u)); }
     }
     {  // EntryTab, `nent` mass-matrix pattern slots: i[], j[], arm[] | lact[], damp[], dcoef[], lcoef[] (implicit only)
       int* k = r + SMJ_LR_ENT;
       for (int u = 0; u < nent; u++) {
-        const int e = L + 64 * u, ok = e < m.nldl, ex = ok ? e : 0, i = gi("k_ldl_i", ex), j = gi("k_ldl_j", ex);
-        k[u] = ok ? i : -1; k[nent + u] = ok ? j : 0; k[2 * nent + u] = fb((ok && i == j) ? gf("dof_armature", i) : 0.f);
-        k[3 * nent + u] = ok ? gi("k_ldl_lact", ex) : -1;
-        k[4 * nent + u] = fb(ok ? gf("k_ldl_damp", ex) : 0.f); k[5 * nent + u] = fb(ok ? gf("k_ldl_dcoef", ex) : 0.f); k[6 * nent + u] = fb(ok ? gf("k_ldl_lcoef", ex) : 0.f);
+        const int e = L + 64 * u, ok = e < m.nldl, ex = ok ? e : 0, i = T.gi("k_ldl_i", ex), j = T.gi("k_ldl_j", ex);
+        k[SMJ_ENT_I * nent + u] = ok ? i : -1; k[SMJ_ENT_J * nent + u] = ok ? j : 0; k[SMJ_ENT_ARM * nent + u] = T.fb((ok && i == j) ? T.gf("dof_armature", i) : 0.f);
+        k[SMJ_ENT_LACT * nent + u] = ok ? T.gi("k_ldl_lact", ex) : -1;
+        k[SMJ_ENT_DAMP * nent + u] = T.fb(ok ? T.gf("k_ldl_damp", ex) : 0.f); k[SMJ_ENT_DCOEF * nent + u] = T.fb(ok ? T.gf("k_ldl_dcoef", ex) : 0.f); k[SMJ_ENT_LCOEF * nent + u] = T.fb(ok ? T.gf("k_ldl_lcoef", ex) : 0.f);
       }
     }
     {  // ActTab: dof[4], qadr[4], mom[4], prm[8], flags, gc_body, gc_mlo, gc_mhi, gc_mass, gc_x, gc_y, gc_z
       int* k = r + LR_ACT;
       const int a = L < nu ? L : 0;
       for (int u = 0; u < 4; u++) {
-        const int dd = gi("k_act_dof", 4 * a + u);
-        k[u] = L < nu ? dd : -1; k[4 + u] = dd >= 0 ? gi("k_dof_qposadr", dd) : 0; k[8 + u] = fb(gf("k_act_mom", 4 * a + u));
+        const int dd = T.gi("k_act_dof", 4 * a + u);
+        k[SMJ_ACT_DOF + u] = L < nu ? dd : -1; k[SMJ_ACT_QADR + u] = dd >= 0 ? T.gi("k_dof_qposadr", dd) : 0; k[SMJ_ACT_MOM + u] = T.fb(T.gf("k_act_mom", 4 * a + u));
       }
-      k[12] = fb(gf("actuator_gainprm", 3 * a));
-      for (int q = 0; q < 3; q++) k[13 + q] = fb(gf("actuator_biasprm", 3 * a + q));
-      k[16] = fb(gf("actuator_ctrlrange", 2 * a)); k[17] = fb(gf("actuator_ctrlrange", 2 * a + 1));
-      k[18] = fb(gf("actuator_forcerange", 2 * a)); k[19] = fb(gf("actuator_forcerange", 2 * a + 1));
-      k[20] = (gi("actuator_ctrllimited", a) ? 1 : 0) | (gi("actuator_forcelimited", a) ? 2 : 0) | (gi("actuator_biastype", a) == 1 ? 4 : 0);
-      const int g = L < m.ngc ? gi("k_gc_body", L) : 0;
-      k[21] = g; k[22] = gi("k_body_dofmask_lo", g); k[23] = gi("k_body_dofmask_hi", g);
-      k[24] = fb(L < m.ngc ? gf("body_gcmass", g) : 0.f);
-      for (int q = 0; q < 3; q++) k[25 + q] = fb(gf("body_gcipos", 3 * g + q));
+      k[SMJ_ACT_GAIN] = T.fb(T.gf("actuator_gainprm", 3 * a));
+      for (int q = 0; q < 3; q++) k[SMJ_ACT_BIAS + q] = T.fb(T.gf("actuator_biasprm", 3 * a + q));
+      for (int q = 0; q < 2; q++) { k[SMJ_ACT_CTRLRANGE + q] = T.fb(T.gf("actuator_ctrlrange", 2 * a + q)); k[SMJ_ACT_FORCERANGE + q] = T.fb(T.gf("actuator_forcerange", 2 * a + q)); }
+      k[SMJ_ACT_FLAGS] = (T.gi("actuator_ctrllimited", a) ? 1 : 0) | (T.gi("actuator_forcelimited", a) ? 2 : 0) | (T.gi("actuator_biastype", a) == 1 ? 4 : 0);
+      const int g = L < m.ngc ? T.gi("k_gc_body", L) : 0;
+      k[SMJ_ACT_GC_BODY] = g; k[SMJ_ACT_GC_MLO] = T.gi("k_body_dofmask_lo", g); k[SMJ_ACT_GC_MHI] = T.gi("k_body_dofmask_hi", g);
+      k[SMJ_ACT_GC_MASS] = T.fb(L < m.ngc ? T.gf("body_gcmass", g) : 0.f);
+      for (int q = 0; q < 3; q++) k[SMJ_ACT_GC_POS + q] = T.fb(T.gf("body_gcipos", 3 * g + q));
     }
   }
   return rec;
 }
 
-static inline std::vector<int> smj_build_pprec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
-                                               std::map<std::string, std::vector<float>>& F) {
+static inline std::vector<int> smj_build_pprec(const DevModel& m, SmjHostTables& T) {
   std::vector<int> rec((size_t)(m.nplanepair > 0 ? m.nplanepair : 1) * SMJ_PP_STRIDE, 0);
-  auto fb = [](float v) { int b; memcpy(&b, &v, 4); return b; };
-  auto gi = [&](const char* n, size_t k) { const std::vector<int>& v = I[n]; return k < v.size() ? v[k] : 0; };
-  auto gf = [&](const char* n, size_t k) { const std::vector<float>& v = F[n]; return k < v.size() ? v[k] : 0.f; };
   for (int t = 0; t < m.nplanepair; t++) {
     int* k = rec.data() + (size_t)t * SMJ_PP_STRIDE;
-    const int p = gi("k_planepair", t), g1 = gi("pair_geom1", p), g2 = gi("pair_geom2", p);
-    k[SMJ_PP_PAIR] = p; k[SMJ_PP_G1] = g1; k[SMJ_PP_G2] = g2; k[SMJ_PP_B1] = gi("geom_bodyid", g1); k[SMJ_PP_B2] = gi("geom_bodyid", g2);
-    k[SMJ_PP_T2] = gi("geom_type", g2); k[SMJ_PP_MARGIN] = fb(gf("pair_margin", p)); k[SMJ_PP_RBOUND2] = fb(gf("geom_rbound", g2));
+    const int p = T.gi("k_planepair", t), g1 = T.gi("pair_geom1", p), g2 = T.gi("pair_geom2", p);
+    k[SMJ_PP_PAIR] = p; k[SMJ_PP_G1] = g1; k[SMJ_PP_G2] = g2; k[SMJ_PP_B1] = T.gi("geom_bodyid", g1); k[SMJ_PP_B2] = T.gi("geom_bodyid", g2);
+    k[SMJ_PP_T2] = T.gi("geom_type", g2); k[SMJ_PP_MARGIN] = T.fb(T.gf("pair_margin", p)); k[SMJ_PP_RBOUND2] = T.fb(T.gf("geom_rbound", g2));
     for (int q = 0; q < 3; q++) {
-      k[SMJ_PP_BCEN2 + q] = fb(gf("k_geom_bcenter", 3 * g2 + q));
-      k[SMJ_PP_POS1 + q] = fb(gf("geom_pos", 3 * g1 + q)); k[SMJ_PP_POS2 + q] = fb(gf("geom_pos", 3 * g2 + q));
-      k[SMJ_PP_SIZE2 + q] = fb(gf("geom_size", 3 * g2 + q));
+      k[SMJ_PP_BCEN2 + q] = T.fb(T.gf("k_geom_bcenter", 3 * g2 + q));
+      k[SMJ_PP_POS1 + q] = T.fb(T.gf("geom_pos", 3 * g1 + q)); k[SMJ_PP_POS2 + q] = T.fb(T.gf("geom_pos", 3 * g2 + q));
+      k[SMJ_PP_SIZE2 + q] = T.fb(T.gf("geom_size", 3 * g2 + q));
     }
-    for (int q = 0; q < 9; q++) { k[SMJ_PP_MAT1 + q] = fb(gf("k_geom_mat", 9 * g1 + q)); k[SMJ_PP_MAT2 + q] = fb(gf("k_geom_mat", 9 * g2 + q)); }
-    k[SMJ_PP_CONDIM] = gi("pair_condim", p); k[SMJ_PP_MG] = fb(gf("pair_margin", p) - gf("pair_gap", p));
-    for (int q = 0; q < 5; q++) { k[SMJ_PP_FRIC + q] = fb(gf("pair_friction", 5 * p + q)); k[SMJ_PP_SOLIMP + q] = fb(gf("pair_solimp", 5 * p + q)); }
-    k[SMJ_PP_SOLREF] = fb(gf("pair_solref", 2 * p)); k[SMJ_PP_SOLREF + 1] = fb(gf("pair_solref", 2 * p + 1));
-    for (int q = 0; q < 6; q++) k[SMJ_PP_BOX2 + q] = fb(gf("geom_aabb", 6 * g2 + q));
+    for (int q = 0; q < 9; q++) { k[SMJ_PP_MAT1 + q] = T.fb(T.gf("k_geom_mat", 9 * g1 + q)); k[SMJ_PP_MAT2 + q] = T.fb(T.gf("k_geom_mat", 9 * g2 + q)); }
+    k[SMJ_PP_CONDIM] = T.gi("pair_condim", p); k[SMJ_PP_MG] = T.fb(T.gf("pair_margin", p) - T.gf("pair_gap", p));
+    for (int q = 0; q < 5; q++) { k[SMJ_PP_FRIC + q] = T.fb(T.gf("pair_friction", 5 * p + q)); k[SMJ_PP_SOLIMP + q] = T.fb(T.gf("pair_solimp", 5 * p + q)); }
+    k[SMJ_PP_SOLREF] = T.fb(T.gf("pair_solref", 2 * p)); k[SMJ_PP_SOLREF + 1] = T.fb(T.gf("pair_solref", 2 * p + 1));
+    for (int q = 0; q < 6; q++) k[SMJ_PP_BOX2 + q] = T.fb(T.gf("geom_aabb", 6 * g2 + q));
   }
   return rec;
 }
-static inline std::vector<int> smj_build_cgrec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
-                                               std::map<std::string, std::vector<float>>& F, bool stat = false) {
+static inline std::vector<int> smj_build_cgrec(const DevModel& m, SmjHostTables& T, bool stat = false) {
   const int ncg = stat ? m.nsgeom : m.ncgeom;
   std::vector<int> rec((size_t)(ncg > 0 ? ncg : 1) * SMJ_CG_STRIDE, 0);
-  auto fb = [](float v) { int b; memcpy(&b, &v, 4); return b; };
-  auto gi = [&](const char* n, size_t k) { const std::vector<int>& v = I[n]; return k < v.size() ? v[k] : 0; };
-  auto gf = [&](const char* n, size_t k) { const std::vector<float>& v = F[n]; return k < v.size() ? v[k] : 0.f; };
   for (int c = 0; c < ncg; c++) {
     int* k = rec.data() + (size_t)c * SMJ_CG_STRIDE;
-    const int g = gi(stat ? "k_sgeom" : "k_cgeom", c), adr = gi("geom_hulladr", g);
-    k[SMJ_CG_GEOM] = g; k[SMJ_CG_BODY] = gi("geom_bodyid", g);
-    k[SMJ_CG_META] = (int)((unsigned)gi("geom_type", g) | ((unsigned)gi("geom_hullnum", g) << 4) | ((unsigned)(adr < 0 ? 0 : adr) << 16));
+    const int g = T.gi(stat ? "k_sgeom" : "k_cgeom", c), adr = T.gi("geom_hulladr", g);
+    k[SMJ_CG_GEOM] = g; k[SMJ_CG_BODY] = T.gi("geom_bodyid", g);
+    k[SMJ_CG_META] = (int)((unsigned)T.gi("geom_type", g) | ((unsigned)T.gi("geom_hullnum", g) << 4) | ((unsigned)(adr < 0 ? 0 : adr) << 16));
     for (int q = 0; q < 3; q++) {
-      k[SMJ_CG_POS + q] = fb(gf("geom_pos", 3 * g + q)); k[SMJ_CG_LCEN + q] = fb(gf("geom_aabb", 6 * g + q));
-      k[SMJ_CG_HALF + q] = fb(gf("geom_aabb", 6 * g + 3 + q)); k[SMJ_CG_CCEN + q] = fb(gf("geom_ccenter", 3 * g + q));
-      k[SMJ_CG_SIZE + q] = fb(gf("geom_size", 3 * g + q));
+      k[SMJ_CG_POS + q] = T.fb(T.gf("geom_pos", 3 * g + q)); k[SMJ_CG_LCEN + q] = T.fb(T.gf("geom_aabb", 6 * g + q));
+      k[SMJ_CG_HALF + q] = T.fb(T.gf("geom_aabb", 6 * g + 3 + q)); k[SMJ_CG_CCEN + q] = T.fb(T.gf("geom_ccenter", 3 * g + q));
+      k[SMJ_CG_SIZE + q] = T.fb(T.gf("geom_size", 3 * g + q));
     }
-    for (int q = 0; q < 9; q++) k[SMJ_CG_MAT + q] = fb(gf("k_geom_mat", 9 * g + q));
-    k[SMJ_CG_RBOUND] = fb(gf("geom_rbound", g));
+    for (int q = 0; q < 9; q++) k[SMJ_CG_MAT + q] = T.fb(T.gf("k_geom_mat", 9 * g + q));
+    k[SMJ_CG_RBOUND] = T.fb(T.gf("geom_rbound", g));
   }
   return rec;
 }
 
-static inline std::vector<int> smj_build_rowrec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
-                                                std::map<std::string, std::vector<float>>& F) {
+static inline std::vector<int> smj_build_rowrec(const DevModel& m, SmjHostTables& T) {
   const int nstat = m.neq + m.nfric, n = nstat + 2 * m.nlimit;
   std::vector<int> rec((size_t)(n > 0 ? n : 1) * SMJ_RR_STRIDE, 0);
-  auto fb = [](float v) { int b; memcpy(&b, &v, 4); return b; };
-  auto gi = [&](const char* nm, size_t k) { const std::vector<int>& v = I[nm]; return k < v.size() ? v[k] : 0; };
-  auto gf = [&](const char* nm, size_t k) { const std::vector<float>& v = F[nm]; return k < v.size() ? v[k] : 0.f; };
   for (int e = 0; e < m.neq; e++) {      // CT_EQUALITY = 0 (joint equalities)
     int* k = rec.data() + (size_t)e * SMJ_RR_STRIDE;
-    const int j1 = gi("eq_obj1id", e), j2 = gi("eq_obj2id", e), q1 = gi("jnt_qposadr", j1), d1 = gi("jnt_dofadr", j1);
-    k[SMJ_RR_TYPE] = 0; k[SMJ_RR_ID] = e; k[SMJ_RR_D1] = d1; k[SMJ_RR_Q1] = q1; k[SMJ_RR_V1] = fb(gf("qpos0", q1));
-    float diag = gf("dof_invweight0", d1);
+    const int j1 = T.gi("eq_obj1id", e), j2 = T.gi("eq_obj2id", e), q1 = T.gi("jnt_qposadr", j1), d1 = T.gi("jnt_dofadr", j1);
+    k[SMJ_RR_TYPE] = 0; k[SMJ_RR_ID] = e; k[SMJ_RR_SAT] = -1; k[SMJ_RR_D1] = d1; k[SMJ_RR_Q1] = q1; k[SMJ_RR_V1] = T.fb(T.gf("qpos0", q1));
+    float diag = T.gf("dof_invweight0", d1);
     if (j2 >= 0) {
-      const int q2 = gi("jnt_qposadr", j2), d2 = gi("jnt_dofadr", j2);
-      k[SMJ_RR_D2] = d2; k[SMJ_RR_Q2] = q2; k[SMJ_RR_V2] = fb(gf("qpos0", q2));
-      diag += gf("dof_invweight0", d2);
+      const int q2 = T.gi("jnt_qposadr", j2), d2 = T.gi("jnt_dofadr", j2);
+      k[SMJ_RR_D2] = d2; k[SMJ_RR_Q2] = q2; k[SMJ_RR_V2] = T.fb(T.gf("qpos0", q2));
+      diag += T.gf("dof_invweight0", d2);
     } else { k[SMJ_RR_D2] = -1; k[SMJ_RR_Q2] = 0; }
-    for (int q = 0; q < 5; q++) { k[SMJ_RR_DATA + q] = fb(gf("eq_data", 5 * e + q)); k[SMJ_RR_SOLIMP + q] = fb(gf("eq_solimp", 5 * e + q)); }
-    k[SMJ_RR_DIAG] = fb(diag);
-    k[SMJ_RR_SOLREF] = fb(gf("eq_solref", 2 * e)); k[SMJ_RR_SOLREF + 1] = fb(gf("eq_solref", 2 * e + 1));
+    for (int q = 0; q < 5; q++) { k[SMJ_RR_DATA + q] = T.fb(T.gf("eq_data", 5 * e + q)); k[SMJ_RR_SOLIMP + q] = T.fb(T.gf("eq_solimp", 5 * e + q)); }
+    k[SMJ_RR_DIAG] = T.fb(diag);
+    k[SMJ_RR_SOLREF] = T.fb(T.gf("eq_solref", 2 * e)); k[SMJ_RR_SOLREF + 1] = T.fb(T.gf("eq_solref", 2 * e + 1));
   }
   // (satellite of a dof / its index inside it; -1, 0 for dofs of the main tree)
   auto sat_of = [&](int d, int* local) {
     *local = 0;
     for (int sidx = 0; sidx < m.nsat; sidx++) {
-      const int da = gi("k_sat_i", 8 * sidx + 3), nd = gi("k_sat_i", 8 * sidx + 4);
+      const int da = T.gi("k_sat_i", SMJ_SAT_I_STRIDE * sidx + SMJ_SR_DADR), nd = T.gi("k_sat_i", SMJ_SAT_I_STRIDE * sidx + SMJ_SR_NDOF);
       if (d >= da && d < da + nd) { *local = d - da; return sidx; }
     }
     return -1;
   };
-  for (int e = 0; e < m.neq; e++) rec[(size_t)e * SMJ_RR_STRIDE + SMJ_RR_SAT] = -1;
   for (int f = 0; f < m.nfric; f++) {    // CT_FRICTION = 1
     int* k = rec.data() + (size_t)(m.neq + f) * SMJ_RR_STRIDE;
-    const int d = gi("k_fric_dof", f);
+    const int d = T.gi("k_fric_dof", f);
     k[SMJ_RR_SAT] = sat_of(d, &k[SMJ_RR_SDOF]);
     k[SMJ_RR_TYPE] = 1; k[SMJ_RR_ID] = d; k[SMJ_RR_D1] = d; k[SMJ_RR_D2] = -1;
-    k[SMJ_RR_DIAG] = fb(gf("dof_invweight0", d)); k[SMJ_RR_FLOSS] = fb(gf("dof_frictionloss", d));
-    k[SMJ_RR_SOLREF] = fb(gf("dof_solref", 2 * d)); k[SMJ_RR_SOLREF + 1] = fb(gf("dof_solref", 2 * d + 1));
-    for (int q = 0; q < 5; q++) k[SMJ_RR_SOLIMP + q] = fb(gf("dof_solimp", 5 * d + q));
+    k[SMJ_RR_DIAG] = T.fb(T.gf("dof_invweight0", d)); k[SMJ_RR_FLOSS] = T.fb(T.gf("dof_frictionloss", d));
+    k[SMJ_RR_SOLREF] = T.fb(T.gf("dof_solref", 2 * d)); k[SMJ_RR_SOLREF + 1] = T.fb(T.gf("dof_solref", 2 * d + 1));
+    for (int q = 0; q < 5; q++) k[SMJ_RR_SOLIMP + q] = T.fb(T.gf("dof_solimp", 5 * d + q));
   }
   for (int L = 0; L < 2 * m.nlimit; L++) {   // CT_LIMIT = 3; slot L = (joint, side), lower side first
     int* k = rec.data() + (size_t)(nstat + L) * SMJ_RR_STRIDE;
-    const int j = gi("k_limit_jnt", L >> 1), d = gi("jnt_dofadr", j);
+    const int j = T.gi("k_limit_jnt", L >> 1), d = T.gi("jnt_dofadr", j);
     k[SMJ_RR_SAT] = sat_of(d, &k[SMJ_RR_SDOF]);
-    k[SMJ_RR_TYPE] = 3; k[SMJ_RR_ID] = j; k[SMJ_RR_D1] = d; k[SMJ_RR_D2] = (L & 1) ? 1 : -1; k[SMJ_RR_Q1] = gi("jnt_qposadr", j);
-    k[SMJ_RR_V1] = fb(gf("jnt_range", 2 * j + (L & 1))); k[SMJ_RR_V2] = fb(gf("jnt_margin", j));
-    k[SMJ_RR_DIAG] = fb(gf("dof_invweight0", d));
-    k[SMJ_RR_SOLREF] = fb(gf("jnt_solref", 2 * j)); k[SMJ_RR_SOLREF + 1] = fb(gf("jnt_solref", 2 * j + 1));
-    for (int q = 0; q < 5; q++) k[SMJ_RR_SOLIMP + q] = fb(gf("jnt_solimp", 5 * j + q));
+    k[SMJ_RR_TYPE] = 3; k[SMJ_RR_ID] = j; k[SMJ_RR_D1] = d; k[SMJ_RR_D2] = (L & 1) ? 1 : -1; k[SMJ_RR_Q1] = T.gi("jnt_qposadr", j);
+    k[SMJ_RR_V1] = T.fb(T.gf("jnt_range", 2 * j + (L & 1))); k[SMJ_RR_V2] = T.fb(T.gf("jnt_margin", j));
+    k[SMJ_RR_DIAG] = T.fb(T.gf("dof_invweight0", d));
+    k[SMJ_RR_SOLREF] = T.fb(T.gf("jnt_solref", 2 * j)); k[SMJ_RR_SOLREF + 1] = T.fb(T.gf("jnt_solref", 2 * j + 1));
+    for (int q = 0; q < 5; q++) k[SMJ_RR_SOLIMP + q] = T.fb(T.gf("jnt_solimp", 5 * j + q));
   }
   return rec;
 }
 
-static inline std::vector<int> smj_build_cprec(const DevModel& m, std::map<std::string, std::vector<int>>& I,
-                                               std::map<std::string, std::vector<float>>& F, bool stat = false) {
+static inline std::vector<int> smj_build_cprec(const DevModel& m, SmjHostTables& T, bool stat = false) {
   const int np = stat ? m.nstatpair : m.nconvpair;
   std::vector<int> rec((size_t)(np > 0 ? np : 1) * SMJ_CP_STRIDE, 0);
-  auto fb = [](float v) { int b; memcpy(&b, &v, 4); return b; };
-  auto gi = [&](const char* nm, size_t k) { const std::vector<int>& v = I[nm]; return k < v.size() ? v[k] : 0; };
-  auto gf = [&](const char* nm, size_t k) { const std::vector<float>& v = F[nm]; return k < v.size() ? v[k] : 0.f; };
   std::map<int, int> dslot, sslot;   // static pairs: geom -> cache slot of the moving geom / index of the static geom
   if (stat) {
-    for (int c = 0; c < m.ncgeom; c++) dslot[gi("k_cgeom", c)] = c;
-    for (int c = 0; c < m.nsgeom; c++) sslot[gi("k_sgeom", c)] = c;
+    for (int c = 0; c < m.ncgeom; c++) dslot[T.gi("k_cgeom", c)] = c;
+    for (int c = 0; c < m.nsgeom; c++) sslot[T.gi("k_sgeom", c)] = c;
   }
   for (int t = 0; t < np; t++) {
     int* k = rec.data() + (size_t)t * SMJ_CP_STRIDE;
-    const int p = gi(stat ? "k_statpair" : "k_convpair", t);
-    k[SMJ_CP_PAIR] = p; k[SMJ_CP_G1] = gi("pair_geom1", p); k[SMJ_CP_G2] = gi("pair_geom2", p);
+    const int p = T.gi(stat ? "k_statpair" : "k_convpair", t);
+    k[SMJ_CP_PAIR] = p; k[SMJ_CP_G1] = T.gi("pair_geom1", p); k[SMJ_CP_G2] = T.gi("pair_geom2", p);
     if (stat) {
       k[SMJ_CP_S1] = sslot.count(k[SMJ_CP_G1]) ? -1 - sslot[k[SMJ_CP_G1]] : dslot[k[SMJ_CP_G1]];
       k[SMJ_CP_S2] = sslot.count(k[SMJ_CP_G2]) ? -1 - sslot[k[SMJ_CP_G2]] : dslot[k[SMJ_CP_G2]];
-    } else { k[SMJ_CP_S1] = gi("k_convpair_s1", t); k[SMJ_CP_S2] = gi("k_convpair_s2", t); }
-    k[SMJ_CP_MARGIN] = fb(gf("pair_margin", p)); k[SMJ_CP_MG] = fb(gf("pair_margin", p) - gf("pair_gap", p)); k[SMJ_CP_CONDIM] = gi("pair_condim", p);
-    for (int q = 0; q < 5; q++) { k[SMJ_CP_FRIC + q] = fb(gf("pair_friction", 5 * p + q)); k[SMJ_CP_SOLIMP + q] = fb(gf("pair_solimp", 5 * p + q)); }
-    k[SMJ_CP_SOLREF] = fb(gf("pair_solref", 2 * p)); k[SMJ_CP_SOLREF + 1] = fb(gf("pair_solref", 2 * p + 1));
-    const float r1 = gf("geom_rbound", k[SMJ_CP_G1]), r2 = gf("geom_rbound", k[SMJ_CP_G2]);
-    k[SMJ_CP_RBMIN] = fb(r1 < r2 ? r1 : r2);
-    k[SMJ_CP_B1] = gi("geom_bodyid", k[SMJ_CP_G1]); k[SMJ_CP_B2] = gi("geom_bodyid", k[SMJ_CP_G2]);
+    } else { k[SMJ_CP_S1] = T.gi("k_convpair_s1", t); k[SMJ_CP_S2] = T.gi("k_convpair_s2", t); }
+    k[SMJ_CP_MARGIN] = T.fb(T.gf("pair_margin", p)); k[SMJ_CP_MG] = T.fb(T.gf("pair_margin", p) - T.gf("pair_gap", p)); k[SMJ_CP_CONDIM] = T.gi("pair_condim", p);
+    for (int q = 0; q < 5; q++) { k[SMJ_CP_FRIC + q] = T.fb(T.gf("pair_friction", 5 * p + q)); k[SMJ_CP_SOLIMP + q] = T.fb(T.gf("pair_solimp", 5 * p + q)); }
+    k[SMJ_CP_SOLREF] = T.fb(T.gf("pair_solref", 2 * p)); k[SMJ_CP_SOLREF + 1] = T.fb(T.gf("pair_solref", 2 * p + 1));
+    const float r1 = T.gf("geom_rbound", k[SMJ_CP_G1]), r2 = T.gf("geom_rbound", k[SMJ_CP_G2]);
+    k[SMJ_CP_RBMIN] = T.fb(r1 < r2 ? r1 : r2);
+    k[SMJ_CP_B1] = T.gi("geom_bodyid", k[SMJ_CP_G1]); k[SMJ_CP_B2] = T.gi("geom_bodyid", k[SMJ_CP_G2]);
   }
   return rec;
+}
+
+// One table of the blob as host words: an i32 entry as it stands, an f64 entry rounded to fp32; never empty (a table without elements
+// is one zero word).  false: the blob has no entry of that name and type.
+static inline bool smj_read_i32(const SmjBlob& b, const char* name, std::vector<int>& h) {
+  const SmjBlobEntry* e = b.find(name);
+  if (!e || e->dtype != 1) return false;
+  h.assign(e->nbytes / 4 ? e->nbytes / 4 : 1, 0);
+  memcpy(h.data(), b.p + e->offset, e->nbytes / 4 * 4);
+  return true;
+}
+static inline bool smj_read_f64(const SmjBlob& b, const char* name, std::vector<float>& h) {
+  const SmjBlobEntry* e = b.find(name);
+  if (!e || e->dtype != 0) return false;
+  const size_t cnt = e->nbytes / 8;
+  h.assign(cnt ? cnt : 1, 0.f);
+  const double* src = reinterpret_cast<const double*>(b.p + e->offset);
+  for (size_t i = 0; i < cnt; i++) h[i] = (float)src[i];
+  return true;
+}
+
+// Defaults of the solver options (SMJ_SOLVER_OPTIONS) and of the two per-launch fields; after the model's dimensions are known.
+static inline void smj_solver_defaults(DevModel& m) {
+  m.row_limit = 0;
+  m.pgs_cap = 0;
+  m.warmstart = 1;
+  m.pgs_fixed_iter = 0;
+  m.qcqp_exact = 0;
+  m.grad_noise = 4e-6f;
+  m.pgs_island_stop = 1;
+  m.pgs_dual_ws = 1;
+  m.max_con_pair = 4;
+  m.solver = 0;
+  m.convex_pairs = 1;
+  m.multiccd = 1;
+  m.sep_cache = getenv("SMJ_NO_SEPCACHE") ? 0 : 1;
+  // pays where free objects rest; a robot alone (<= 32 dofs) has no resting convex pair and the lookup cost the headline 1 %
+  m.manifold_cache = (getenv("SMJ_NO_MCACHE") || m.nv_all <= 32) ? 0 : 1;
+  m.multi_serial = 0;
+  m.ls_iterations = 50;
+  m.ls_tolerance = 0.01f;
 }
 
 // `caps`: the kernel variants available to the caller, smallest first; the first one the model fits is chosen (*chosen).
@@ -342,18 +371,13 @@ int smj_load_model(const void* blob, size_t nbytes, DevModel& m, Up& up, std::st
 #undef GI
 #undef GF
   if (m.nsat > 0 && (m.ngeom >= 65536 || m.npair >= (1 << 19))) { err = "satellite builds: at most 65535 geoms and 524287 collision pairs (16-bit geom ids per contact, the PGS row key)"; return -4; }
-  {
-    const SmjBlobEntry* e = b.find("sensor_lidar_site");
-    m.nlidar = e ? (int)(e->nbytes / 4) : 0;
-  }
-  m.row_limit = 0; m.pgs_cap = 0; m.warmstart = 1; m.pgs_fixed_iter = 0; m.qcqp_exact = 0; m.grad_noise = 4e-6f; m.pgs_island_stop = 1; m.pgs_dual_ws = 1; m.max_con_pair = 4; m.solver = 0; m.convex_pairs = 1; m.multiccd = 1; m.sep_cache = getenv("SMJ_NO_SEPCACHE") ? 0 : 1; m.manifold_cache = (getenv("SMJ_NO_MCACHE") || m.nv_all <= 32) ? 0 : 1;   /* pays where free objects rest; a robot alone (<= 32 dofs) has no resting convex pair and the lookup cost the headline 1 % */ m.multi_serial = 0; m.ls_iterations = 50; m.ls_tolerance = 0.01f;
+  const SmjBlobEntry* lidar = b.find("sensor_lidar_site");
+  m.nlidar = lidar ? (int)(lidar->nbytes / 4) : 0;
+  smj_solver_defaults(m);
   char buf[256];
-  int hint = 0;
-  {   // optional hint of the model compiler: contact-rich scene (smj_pick_variant)
-    const SmjBlobEntry* e = b.find("k_capacity_hint");
-    if (e && e->dtype == 1 && e->nbytes >= 4) memcpy(&hint, b.p + e->offset, 4);
-  }
-  const int pick = smj_pick_variant(m, hint, caps, ncaps);
+  std::vector<int> hint(1, 0);   // optional hint of the model compiler: contact-rich scene (smj_pick_variant)
+  smj_read_i32(b, "k_capacity_hint", hint);
+  const int pick = smj_pick_variant(m, hint[0], caps, ncaps);
   if (pick < 0 || m.nu > 16) {
     const SmjCaps& c = caps[ncaps - 1];
     snprintf(buf, sizeof buf, "model exceeds kernel capacity (nv %d<=%d, nbody %d<=%d, nq %d<=%d, nu %d<=16, mass-matrix entries %d<=%d, satellites %d)",
@@ -369,32 +393,15 @@ int smj_load_model(const void* blob, size_t nbytes, DevModel& m, Up& up, std::st
   if (m.njump > 6) { err = "body tree deeper than 64 levels"; return -4; }
   if (m.ncgeom > NCG) { err = "too many geoms in non-plane collision pairs"; return -4; }
   if (m.nconvpair >= 65536) { err = "more than 65535 non-plane collision pairs (the survivor list holds 16-bit pair indices)"; return -4; }
-  std::map<std::string, std::vector<int>> hosti;
-  std::map<std::string, std::vector<float>> hostf;
-#define X(n)                                                                               \
-  {                                                                                        \
-    const SmjBlobEntry* e = b.find(#n);                                                    \
-    if (!e || e->dtype != 1) { err = "model blob: missing i32 array " #n; return -3; }     \
-    std::vector<int> h(e->nbytes / 4 ? e->nbytes / 4 : 1, 0);                              \
-    memcpy(h.data(), b.p + e->offset, e->nbytes);                                          \
-    m.n = up.i32(h);                                                                       \
-    hosti[#n] = h;                                                                         \
-    if (!m.n) { err = "device allocation failed for " #n; return -2; }                     \
-  }
+  SmjHostTables T;
+#define X(n)                                                                                     \
+  if (!smj_read_i32(b, #n, T.i[#n])) { err = "model blob: missing i32 array " #n; return -3; }   \
+  if (!(m.n = up.i32(T.i[#n]))) { err = "device allocation failed for " #n; return -2; }
   SMJ_MODEL_I32(X)
 #undef X
-#define X(n)                                                                               \
-  {                                                                                        \
-    const SmjBlobEntry* e = b.find(#n);                                                    \
-    if (!e || e->dtype != 0) { err = "model blob: missing f64 array " #n; return -3; }     \
-    size_t cnt = e->nbytes / 8;                                                            \
-    std::vector<float> h(cnt ? cnt : 1, 0.f);                                              \
-    const double* src = reinterpret_cast<const double*>(b.p + e->offset);                  \
-    for (size_t i = 0; i < cnt; i++) h[i] = (float)src[i];                                 \
-    m.n = up.f32(h);                                                                       \
-    hostf[#n] = h;                                                                         \
-    if (!m.n) { err = "device allocation failed for " #n; return -2; }                     \
-  }
+#define X(n)                                                                                     \
+  if (!smj_read_f64(b, #n, T.f[#n])) { err = "model blob: missing f64 array " #n; return -3; }   \
+  if (!(m.n = up.f32(T.f[#n]))) { err = "device allocation failed for " #n; return -2; }
   SMJ_MODEL_F32(X)
 #undef X
   m.nsgeom = 0; m.nstatpair = 0; m.k_sgrec = m.k_sprec = m.k_spair = m.k_grid_adr = m.k_grid_list = m.k_sg_cell = nullptr; m.k_sg_bound = nullptr; m.k_sgw = nullptr;
@@ -405,95 +412,63 @@ int smj_load_model(const void* blob, size_t nbytes, DevModel& m, Up& up, std::st
     if (m.nsgeom > 0) {
       for (int q = 0; q < 3; q++) { if (!geti("k_grid", q, &m.grid_dim[q]) || !getf("k_grid_f", q, &m.grid_org[q])) return -3; }
       if (!getf("k_grid_f", 3, &m.grid_h) || !getf("k_grid_f", 4, &m.grid_margin)) return -3;
-      auto loadi = [&](const char* name, const int** dst) -> bool {
-        const SmjBlobEntry* e = b.find(name);
-        if (!e || e->dtype != 1) { err = std::string("model blob: missing i32 array ") + name; return false; }
-        std::vector<int> h(e->nbytes / 4 ? e->nbytes / 4 : 1, 0);
-        memcpy(h.data(), b.p + e->offset, e->nbytes);
-        hosti[name] = h;
-        *dst = up.i32(h);
-        return *dst != nullptr;
+      auto loadi = [&](const char* name) -> const int* {   // (k_sgeom, k_statpair: read by the record builders only)
+        if (!smj_read_i32(b, name, T.i[name])) { err = std::string("model blob: missing i32 array ") + name; return nullptr; }
+        return up.i32(T.i[name]);
       };
-      const int* dummy = nullptr;
-      if (!loadi("k_sgeom", &dummy) || !loadi("k_statpair", &dummy) || !loadi("k_spair", &m.k_spair) || !loadi("k_grid_adr", &m.k_grid_adr) ||
-          !loadi("k_grid_list", &m.k_grid_list) || !loadi("k_sg_cell", &m.k_sg_cell)) return err.empty() ? -2 : -3;
-      {
-        const SmjBlobEntry* e = b.find("geom_aabb");   // (already among the float tables: hostf)
-        (void)e;
-      }
-      std::vector<int> sg = smj_build_cgrec(m, hosti, hostf, true), spr = smj_build_cprec(m, hosti, hostf, true);
+      if (!loadi("k_sgeom") || !loadi("k_statpair") || !(m.k_spair = loadi("k_spair")) || !(m.k_grid_adr = loadi("k_grid_adr")) ||
+          !(m.k_grid_list = loadi("k_grid_list")) || !(m.k_sg_cell = loadi("k_sg_cell"))) return err.empty() ? -2 : -3;
+      std::vector<int> sg = smj_build_cgrec(m, T, true), spr = smj_build_cprec(m, T, true);
       m.k_sgrec = up.i32(sg);
       m.k_sprec = up.i32(spr);
-      std::vector<float> bound(8 * (size_t)m.nsgeom, 0.f);   // world AABB of the geom's oriented box: lo xyz, pad, hi xyz, pad
-      std::vector<float> wcen(3 * (size_t)m.nsgeom, 0.f);
+      // each static geom in the world frame (SMJ_SGW_*) and the world AABB of its oriented box (SMJ_SGB_*: lo xyz, pad, hi xyz, pad)
+      std::vector<float> bound(SMJ_SGB_STRIDE * (size_t)m.nsgeom, 0.f), sgw(SMJ_SGW_STRIDE * (size_t)m.nsgeom, 0.f);
       for (int c = 0; c < m.nsgeom; c++) {
         const int* k = sg.data() + (size_t)c * SMJ_CG_STRIDE;
         float f[SMJ_CG_STRIDE];
         memcpy(f, k, sizeof f);
+        float *w = sgw.data() + SMJ_SGW_STRIDE * (size_t)c, *bd = bound.data() + SMJ_SGB_STRIDE * (size_t)c;
         for (int i = 0; i < 3; i++) {
           const float cen = f[SMJ_CG_POS + i] + f[SMJ_CG_MAT + 3 * i] * f[SMJ_CG_LCEN] + f[SMJ_CG_MAT + 3 * i + 1] * f[SMJ_CG_LCEN + 1] + f[SMJ_CG_MAT + 3 * i + 2] * f[SMJ_CG_LCEN + 2];
           const float ext = fabsf(f[SMJ_CG_MAT + 3 * i]) * f[SMJ_CG_HALF] + fabsf(f[SMJ_CG_MAT + 3 * i + 1]) * f[SMJ_CG_HALF + 1] + fabsf(f[SMJ_CG_MAT + 3 * i + 2]) * f[SMJ_CG_HALF + 2];
-          wcen[3 * c + i] = cen;
-          bound[8 * c + i] = cen - ext; bound[8 * c + 4 + i] = cen + ext;
+          bd[SMJ_SGB_LO + i] = cen - ext; bd[SMJ_SGB_HI + i] = cen + ext;
+          w[SMJ_SGW_POS + i] = f[SMJ_CG_POS + i]; w[SMJ_SGW_CEN + i] = cen; w[SMJ_SGW_HALF + i] = f[SMJ_CG_HALF + i]; w[SMJ_SGW_SIZE + i] = f[SMJ_CG_SIZE + i];
+          w[SMJ_SGW_CCEN + i] = f[SMJ_CG_POS + i] + f[SMJ_CG_MAT + 3 * i] * f[SMJ_CG_CCEN] + f[SMJ_CG_MAT + 3 * i + 1] * f[SMJ_CG_CCEN + 1] + f[SMJ_CG_MAT + 3 * i + 2] * f[SMJ_CG_CCEN + 2];
         }
+        for (int i = 0; i < 9; i++) w[SMJ_SGW_MAT + i] = f[SMJ_CG_MAT + i];
+        memcpy(&w[SMJ_SGW_META], &k[SMJ_CG_META], 4);
       }
       m.k_sg_bound = up.f32(bound);
-      std::vector<float> sgw(32 * (size_t)m.nsgeom, 0.f);
-      for (int c = 0; c < m.nsgeom; c++) {
-        const int* k = sg.data() + (size_t)c * SMJ_CG_STRIDE;
-        float f[SMJ_CG_STRIDE];
-        memcpy(f, k, sizeof f);
-        float* w = sgw.data() + 32 * (size_t)c;
-        for (int i = 0; i < 3; i++) {
-          w[i] = f[SMJ_CG_POS + i];
-          w[12 + i] = wcen[3 * c + i];
-          w[15 + i] = f[SMJ_CG_HALF + i];
-          w[18 + i] = f[SMJ_CG_POS + i] + f[SMJ_CG_MAT + 3 * i] * f[SMJ_CG_CCEN] + f[SMJ_CG_MAT + 3 * i + 1] * f[SMJ_CG_CCEN + 1] + f[SMJ_CG_MAT + 3 * i + 2] * f[SMJ_CG_CCEN + 2];
-          w[21 + i] = f[SMJ_CG_SIZE + i];
-        }
-        for (int i = 0; i < 9; i++) w[3 + i] = f[SMJ_CG_MAT + i];
-        memcpy(&w[24], &k[SMJ_CG_META], 4);
-      }
       m.k_sgw = up.f32(sgw);
       if (!m.k_sgrec || !m.k_sprec || !m.k_sg_bound || !m.k_sgw) { err = "device allocation failed for the static-geometry tables"; return -2; }
     }
   }
   m.nfric_main = m.nfric; m.nlimit_main = m.nlimit; m.k_satrec = nullptr;
   if (m.nsat > 0) {
-    const SmjBlobEntry* ei = b.find("k_sat_i");
-    const SmjBlobEntry* ef = b.find("k_sat_f");
-    if (!ei || !ef || ei->dtype != 1 || ef->dtype != 0 || ei->nbytes < 32u * m.nsat || ef->nbytes < 8u * 44u * m.nsat) { err = "model blob: satellite tables missing"; return -3; }
-    std::vector<int> si(8 * (size_t)m.nsat), rec((size_t)m.nsat * SMJ_SR_STRIDE, 0);
-    memcpy(si.data(), b.p + ei->offset, 32u * m.nsat);
-    hosti["k_sat_i"] = si;
-    const double* sf = reinterpret_cast<const double*>(b.p + ef->offset);
+    std::vector<int>& si = T.i["k_sat_i"];
+    std::vector<float> sf;
+    if (!smj_read_i32(b, "k_sat_i", si) || !smj_read_f64(b, "k_sat_f", sf) || si.size() < SMJ_SAT_I_STRIDE * (size_t)m.nsat || sf.size() < SMJ_SAT_F_STRIDE * (size_t)m.nsat) { err = "model blob: satellite tables missing"; return -3; }
+    std::vector<int> rec((size_t)m.nsat * SMJ_SR_STRIDE, 0);
     for (int sidx = 0; sidx < m.nsat; sidx++) {
       int* k = rec.data() + (size_t)sidx * SMJ_SR_STRIDE;
-      for (int q = 0; q < 8; q++) k[q] = si[8 * sidx + q];
-      for (int q = 0; q < 44; q++) { const float v = (float)sf[44 * sidx + q]; memcpy(&k[SMJ_SR_F + q], &v, 4); }
+      for (int q = 0; q < SMJ_SAT_I_STRIDE; q++) k[q] = si[SMJ_SAT_I_STRIDE * sidx + q];
+      for (int q = 0; q < SMJ_SAT_F_STRIDE; q++) k[SMJ_SR_F + q] = T.fb(sf[SMJ_SAT_F_STRIDE * sidx + q]);
     }
     m.k_satrec = up.i32(rec);
     if (!m.k_satrec) { err = "device allocation failed for k_satrec"; return -2; }
     // static rows / limit slots of the main tree come first in their tables (dof / joint order)
-    m.nfric_main = 0;
-    for (int f = 0; f < m.nfric; f++) m.nfric_main += hosti["k_fric_dof"][f] < m.nv;
-    m.nlimit_main = 0;
-    for (int L = 0; L < m.nlimit; L++) m.nlimit_main += hosti["jnt_dofadr"][hosti["k_limit_jnt"][L]] < m.nv;
+    m.nfric_main = m.nlimit_main = 0;
+    for (int f = 0; f < m.nfric; f++) m.nfric_main += T.i["k_fric_dof"][f] < m.nv;
+    for (int L = 0; L < m.nlimit; L++) m.nlimit_main += T.i["jnt_dofadr"][T.i["k_limit_jnt"][L]] < m.nv;
   }
-  {
-    std::vector<int> rec = smj_build_lanerec(m, hosti, hostf, nent);
-    m.k_lanerec = up.i32(rec);
-    if (!m.k_lanerec) { err = "device allocation failed for k_lanerec"; return -2; }
-    std::vector<int> pp = smj_build_pprec(m, hosti, hostf), cg = smj_build_cgrec(m, hosti, hostf);
-    m.k_pprec = up.i32(pp);
-    m.k_cgrec = up.i32(cg);
-    if (!m.k_pprec || !m.k_cgrec) { err = "device allocation failed for the collision records"; return -2; }
-    std::vector<int> rr = smj_build_rowrec(m, hosti, hostf);
-    m.k_rowrec = up.i32(rr);
-    if (!m.k_rowrec) { err = "device allocation failed for k_rowrec"; return -2; }
-    std::vector<int> cp = smj_build_cprec(m, hosti, hostf);
-    m.k_cprec = up.i32(cp);
-    if (!m.k_cprec) { err = "device allocation failed for k_cprec"; return -2; }
-  }
+  m.k_lanerec = up.i32(smj_build_lanerec(m, T, nent));
+  if (!m.k_lanerec) { err = "device allocation failed for k_lanerec"; return -2; }
+  m.k_pprec = up.i32(smj_build_pprec(m, T));
+  m.k_cgrec = up.i32(smj_build_cgrec(m, T));
+  if (!m.k_pprec || !m.k_cgrec) { err = "device allocation failed for the collision records"; return -2; }
+  m.k_rowrec = up.i32(smj_build_rowrec(m, T));
+  if (!m.k_rowrec) { err = "device allocation failed for k_rowrec"; return -2; }
+  m.k_cprec = up.i32(smj_build_cprec(m, T));
+  if (!m.k_cprec) { err = "device allocation failed for k_cprec"; return -2; }
   return 0;
 }

@@ -980,10 +980,10 @@ SMJ_DEV void solve_ext_schur(PL<float>& x, int next) {
 // in cache slot NCG.  Same contacts as the oracle's scan of the whole table (oracle/smj_oracle.c collision()).
 SMJ_DEV void stage_static(int sg) {
   LANES {
-    if (lane < 25) {   // one word per lane: the loader's world-frame record (DevModel::k_sgw) into the cache arrays' staging slot
-      const float v = M.k_sgw[sg * 32 + lane];
-      float* dst = lane < 3 ? &s.u.c.pos[NCG][lane] : lane < 12 ? &s.u.c.mat[NCG][lane - 3] : lane < 15 ? &s.u.c.cen[NCG][lane - 12]
-                 : lane < 18 ? &s.u.c.half[NCG][lane - 15] : lane < 21 ? &s.u.c.ccen[NCG][lane - 18] : lane < 24 ? &s.u.c.size[NCG][lane - 21]
+    if (lane < SMJ_SGW_WORDS) {   // one word per lane: the loader's world-frame record (DevModel::k_sgw) into the cache arrays' staging slot
+      const float v = M.k_sgw[sg * SMJ_SGW_STRIDE + lane];
+      float* dst = lane < SMJ_SGW_MAT ? &s.u.c.pos[NCG][lane - SMJ_SGW_POS] : lane < SMJ_SGW_CEN ? &s.u.c.mat[NCG][lane - SMJ_SGW_MAT] : lane < SMJ_SGW_HALF ? &s.u.c.cen[NCG][lane - SMJ_SGW_CEN]
+                 : lane < SMJ_SGW_CCEN ? &s.u.c.half[NCG][lane - SMJ_SGW_HALF] : lane < SMJ_SGW_SIZE ? &s.u.c.ccen[NCG][lane - SMJ_SGW_CCEN] : lane < SMJ_SGW_META ? &s.u.c.size[NCG][lane - SMJ_SGW_SIZE]
                  : reinterpret_cast<float*>(&s.u.c.meta[NCG]);
       *dst = v;
     }
@@ -1031,7 +1031,7 @@ SMJ_DEV void collision_static(float* pc, bool prof) {
         LANES {
           const int sg = g0 + lane;
           if (sg < nsg) {
-            const Vec4 blo = *reinterpret_cast<const Vec4*>(M.k_sg_bound + 8 * opaque(sg)), bhi = *reinterpret_cast<const Vec4*>(M.k_sg_bound + 8 * opaque(sg) + 4);
+            const Vec4 blo = *reinterpret_cast<const Vec4*>(M.k_sg_bound + SMJ_SGB_STRIDE * opaque(sg) + SMJ_SGB_LO), bhi = *reinterpret_cast<const Vec4*>(M.k_sg_bound + SMJ_SGB_STRIDE * opaque(sg) + SMJ_SGB_HI);
             // eight moving geoms per round: centres / radii fetched first, the tests leave a bit mask, a round with a hit enters the append loop
             for (int c0 = 0; c0 < ncg; c0 += 8) {
               float cx[8], cy[8], cz[8], cr[8];
@@ -1088,11 +1088,11 @@ SMJ_DEV void collision_static(float* pc, bool prof) {
         const int w = cw[r][lane], sg = w & 511, c = w >> 9;
         const int sid = csid[r][lane];
         if (sid >= 0) {
-          const float* sw = M.k_sgw + 32 * sg;
+          const float* sw = M.k_sgw + SMJ_SGW_STRIDE * sg;
           float Rb[9], hb[3], Ra[9], ha[3], Rm[3][3], ta[3], tb[3];
-          for (int q = 0; q < 9; q++) { Rb[q] = sw[3 + q]; Ra[q] = s.u.c.mat[c][q]; }
-          for (int q = 0; q < 3; q++) { hb[q] = sw[15 + q]; ha[q] = s.u.c.half[c][q]; }
-          const float dv[3] = {sw[12] - s.u.c.cen[c][0], sw[13] - s.u.c.cen[c][1], sw[14] - s.u.c.cen[c][2]};
+          for (int q = 0; q < 9; q++) { Rb[q] = sw[SMJ_SGW_MAT + q]; Ra[q] = s.u.c.mat[c][q]; }
+          for (int q = 0; q < 3; q++) { hb[q] = sw[SMJ_SGW_HALF + q]; ha[q] = s.u.c.half[c][q]; }
+          const float dv[3] = {sw[SMJ_SGW_CEN] - s.u.c.cen[c][0], sw[SMJ_SGW_CEN + 1] - s.u.c.cen[c][1], sw[SMJ_SGW_CEN + 2] - s.u.c.cen[c][2]};
           bool hit = true;
           for (int i = 0; i < 3; i++) {
             ta[i] = Ra[i] * dv[0] + Ra[3 + i] * dv[1] + Ra[6 + i] * dv[2];

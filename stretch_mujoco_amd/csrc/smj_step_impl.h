@@ -397,16 +397,16 @@ struct StepKernel {
   SMJ_DEV void load(KinTab& t) {
     LANES {
       const int* r = lanerec(opaque(lane), SMJ_LR_KIN);
-      int v[35];
-      for (int k = 0; k < 35; k++) v[k] = r[k];
-      t.parent[lane] = v[0]; t.level[lane] = v[1];
-      for (int q = 0; q < 6; q++) t.jump[lane][q] = v[2 + q];
-      for (int k = 0; k < 3; k++) t.pos[lane][k] = asf(v[8 + k]);
-      for (int k = 0; k < 4; k++) t.quat[lane][k] = asf(v[11 + k]);
+      int v[SMJ_KIN_WORDS];
+      for (int k = 0; k < SMJ_KIN_WORDS; k++) v[k] = r[k];
+      t.parent[lane] = v[SMJ_KIN_PARENT]; t.level[lane] = v[SMJ_KIN_LEVEL];
+      for (int q = 0; q < 6; q++) t.jump[lane][q] = v[SMJ_KIN_JUMP + q];
+      for (int k = 0; k < 3; k++) t.pos[lane][k] = asf(v[SMJ_KIN_POS + k]);
+      for (int k = 0; k < 4; k++) t.quat[lane][k] = asf(v[SMJ_KIN_QUAT + k]);
       for (int u = 0; u < 2; u++) {
-        t.jtype[lane][u] = v[15 + u]; t.jqadr[lane][u] = v[17 + u]; t.jdadr[lane][u] = v[19 + u]; t.jq0[lane][u] = asf(v[21 + u]);
+        t.jtype[lane][u] = v[SMJ_KIN_JTYPE + u]; t.jqadr[lane][u] = v[SMJ_KIN_JQADR + u]; t.jdadr[lane][u] = v[SMJ_KIN_JDADR + u]; t.jq0[lane][u] = asf(v[SMJ_KIN_JQ0 + u]);
       }
-      for (int k = 0; k < 6; k++) { t.jaxis[lane][k] = asf(v[23 + k]); t.jpos[lane][k] = asf(v[29 + k]); }
+      for (int k = 0; k < 6; k++) { t.jaxis[lane][k] = asf(v[SMJ_KIN_JAXIS + k]); t.jpos[lane][k] = asf(v[SMJ_KIN_JPOS + k]); }
     }
   }
   struct BodyTab {  // lane = body: inertia and tree bookkeeping
@@ -418,12 +418,12 @@ struct StepKernel {
   SMJ_DEV void load(BodyTab& t) {
     LANES {
       const int* r = lanerec(opaque(lane), SMJ_LR_BODY);
-      int v[23];
-      for (int k = 0; k < 23; k++) v[k] = r[k];
-      t.root[lane] = v[0]; t.subsize[lane] = v[1]; t.parent[lane] = v[2]; t.dofadr[lane] = v[3]; t.dofnum[lane] = v[4];
-      for (int q = 0; q < 6; q++) t.jump[lane][q] = v[5 + q];
-      t.dofmask[lane] = mk64(v[11], v[12]);
-      for (int k = 0; k < 10; k++) t.inl[lane][k] = asf(v[13 + k]);
+      int v[SMJ_BODY_WORDS];
+      for (int k = 0; k < SMJ_BODY_WORDS; k++) v[k] = r[k];
+      t.root[lane] = v[SMJ_BODY_ROOT]; t.subsize[lane] = v[SMJ_BODY_SUBSIZE]; t.parent[lane] = v[SMJ_BODY_PARENT]; t.dofadr[lane] = v[SMJ_BODY_DOFADR]; t.dofnum[lane] = v[SMJ_BODY_DOFNUM];
+      for (int q = 0; q < 6; q++) t.jump[lane][q] = v[SMJ_BODY_JUMP + q];
+      t.dofmask[lane] = mk64(v[SMJ_BODY_DOFMASK_LO], v[SMJ_BODY_DOFMASK_HI]);
+      for (int k = 0; k < 10; k++) t.inl[lane][k] = asf(v[SMJ_BODY_INL + k]);
     }
   }
   struct DofTab {   // lane = dof
@@ -436,12 +436,12 @@ struct StepKernel {
   SMJ_DEV void load(DofTab& t) {
     LANES {
       const int* r = lanerec(opaque(lane), SMJ_LR_DOF);
-      int v[14];
-      for (int k = 0; k < 14; k++) v[k] = r[k];
-      t.body[lane] = v[0]; t.jtype[lane] = v[1]; t.qadr[lane] = v[2]; t.first[lane] = v[3]; t.bsub[lane] = v[4];
-      t.velmask[lane] = mk64(v[5], v[6]);
-      t.damp[lane] = asf(v[7]); t.stiff[lane] = asf(v[8]); t.spring[lane] = asf(v[9]);
-      for (int u = 0; u < 2; u++) { t.act[lane][u] = v[10 + u]; t.actmom[lane][u] = asf(v[12 + u]); }
+      int v[SMJ_DOF_WORDS];
+      for (int k = 0; k < SMJ_DOF_WORDS; k++) v[k] = r[k];
+      t.body[lane] = v[SMJ_DOF_BODY]; t.jtype[lane] = v[SMJ_DOF_JTYPE]; t.qadr[lane] = v[SMJ_DOF_QADR]; t.first[lane] = v[SMJ_DOF_FIRST]; t.bsub[lane] = v[SMJ_DOF_BSUB];
+      t.velmask[lane] = mk64(v[SMJ_DOF_VELMASK_LO], v[SMJ_DOF_VELMASK_HI]);
+      t.damp[lane] = asf(v[SMJ_DOF_DAMP]); t.stiff[lane] = asf(v[SMJ_DOF_STIFF]); t.spring[lane] = asf(v[SMJ_DOF_SPRING]);
+      for (int u = 0; u < 2; u++) { t.act[lane][u] = v[SMJ_DOF_ACT + u]; t.actmom[lane][u] = asf(v[SMJ_DOF_ACTMOM + u]); }
     }
   }
   struct EntryTab { // lane = mass-matrix pattern slots (NENT per lane)
@@ -451,11 +451,11 @@ struct StepKernel {
   SMJ_DEV void load(EntryTab& t, bool implicit) {
     LANES {
       const int* r = lanerec(opaque(lane), SMJ_LR_ENT);
-      for (int u = 0; u < NENT; u++) { t.i[lane][u] = r[u]; t.j[lane][u] = r[NENT + u]; t.arm[lane][u] = asf(r[2 * NENT + u]); }
+      for (int u = 0; u < NENT; u++) { t.i[lane][u] = r[SMJ_ENT_I * NENT + u]; t.j[lane][u] = r[SMJ_ENT_J * NENT + u]; t.arm[lane][u] = asf(r[SMJ_ENT_ARM * NENT + u]); }
       if (implicit)
         for (int u = 0; u < NENT; u++) {
-          t.lact[lane][u] = r[3 * NENT + u]; t.damp[lane][u] = asf(r[4 * NENT + u]); t.dcoef[lane][u] = asf(r[5 * NENT + u]);
-          t.lcoef[lane][u] = asf(r[6 * NENT + u]);
+          t.lact[lane][u] = r[SMJ_ENT_LACT * NENT + u]; t.damp[lane][u] = asf(r[SMJ_ENT_DAMP * NENT + u]); t.dcoef[lane][u] = asf(r[SMJ_ENT_DCOEF * NENT + u]);
+          t.lcoef[lane][u] = asf(r[SMJ_ENT_LCOEF * NENT + u]);
         }
     }
   }
@@ -470,12 +470,12 @@ struct StepKernel {
   SMJ_DEV void load(ActTab& t) {
     LANES {
       const int* r = lanerec(opaque(lane), SMJ_LR_ACT);
-      int v[28];
-      for (int k = 0; k < 28; k++) v[k] = r[k];
-      for (int u = 0; u < 4; u++) { t.dof[lane][u] = v[u]; t.qadr[lane][u] = v[4 + u]; t.mom[lane][u] = asf(v[8 + u]); }
-      for (int k = 0; k < 8; k++) t.prm[lane][k] = asf(v[12 + k]);
-      t.flags[lane] = v[20]; t.gc_body[lane] = v[21]; t.gc_mlo[lane] = v[22]; t.gc_mhi[lane] = v[23];
-      t.gc_mass[lane] = asf(v[24]); t.gc_x[lane] = asf(v[25]); t.gc_y[lane] = asf(v[26]); t.gc_z[lane] = asf(v[27]);
+      int v[SMJ_ACT_WORDS];
+      for (int k = 0; k < SMJ_ACT_WORDS; k++) v[k] = r[k];
+      for (int u = 0; u < 4; u++) { t.dof[lane][u] = v[SMJ_ACT_DOF + u]; t.qadr[lane][u] = v[SMJ_ACT_QADR + u]; t.mom[lane][u] = asf(v[SMJ_ACT_MOM + u]); }
+      for (int k = 0; k < 8; k++) t.prm[lane][k] = asf(v[SMJ_ACT_PRM + k]);
+      t.flags[lane] = v[SMJ_ACT_FLAGS]; t.gc_body[lane] = v[SMJ_ACT_GC_BODY]; t.gc_mlo[lane] = v[SMJ_ACT_GC_MLO]; t.gc_mhi[lane] = v[SMJ_ACT_GC_MHI];
+      t.gc_mass[lane] = asf(v[SMJ_ACT_GC_MASS]); t.gc_x[lane] = asf(v[SMJ_ACT_GC_POS]); t.gc_y[lane] = asf(v[SMJ_ACT_GC_POS + 1]); t.gc_z[lane] = asf(v[SMJ_ACT_GC_POS + 2]);
     }
   }
 

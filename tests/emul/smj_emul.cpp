@@ -18,19 +18,7 @@
 #include "../../stretch_mujoco_amd/csrc/smj_model_load.h"
 #include "../../stretch_mujoco_amd/csrc/smj_step_impl.h"
 #include "../../stretch_mujoco_amd/csrc/smj_variants.h"
-
-struct HostUploader {
-  std::vector<void*>* keep;
-  template <class T>
-  const T* put(const std::vector<T>& h) {
-    T* p = (T*)malloc(h.size() * sizeof(T));
-    memcpy(p, h.data(), h.size() * sizeof(T));
-    keep->push_back(p);
-    return p;
-  }
-  const float* f32(const std::vector<float>& h) { return put(h); }
-  const int* i32(const std::vector<int>& h) { return put(h); }
-};
+#include "../host_uploader.h"
 
 struct emul_ctx {
   DevModel m{};

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../host_uploader.h"
 #include "smj_model_load.h"
 #include "smj_variants.h"
 
@@ -21,18 +22,6 @@ static const SmjBuildDesc* const builds[SMJ_B_COUNT] = {
 #define X(tag) &probe_product_##tag,
     SMJ_BUILDS(X)
 #undef X
-};
-struct HostUploader {
-  std::vector<void*>* keep;
-  template <class T>
-  const T* put(const std::vector<T>& h) {
-    T* p = (T*)malloc(h.size() * sizeof(T) + 1);
-    memcpy(p, h.data(), h.size() * sizeof(T));
-    keep->push_back(p);
-    return p;
-  }
-  const float* f32(const std::vector<float>& h) { return put(h); }
-  const int* i32(const std::vector<int>& h) { return put(h); }
 };
 
 int main(int argc, char** argv) {

@@ -50,4 +50,5 @@ int smj_costmap_to_navigation(smj_ctx* ctx, const void* cost_dev, const void* go
 #ifdef __cplusplus
 }
 #endif
+#include "smj_frontier.h"
 #endif

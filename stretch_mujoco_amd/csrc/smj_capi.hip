@@ -27,6 +27,7 @@
 #include "smj_occ.h"
 #include "smj_edt.h"
 #include "smj_nav.h"
+#include "smj_front.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -809,6 +810,28 @@ int smj_costmap_to_navigation(smj_ctx* c, const void* cost_dev, const void* goal
   HIPCHK(c, hipSetDevice(c->device));
   smj_launch_nav(c->num_envs, (const uint8_t*)cost_dev, (const int*)goal_dev, num_goals, nx, ny, lethal, neutral, (int*)potential_dev,
                  (int*)next_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int smj_occupancy_to_frontiers(smj_ctx* c, const void* hit_dev, const void* miss_dev, const void* cost_dev, int nx, int ny, int min_hits, int lethal,
+                               int min_size, int max_regions, void* label_dev, void* goal_dev, void* region_dev, void* count_dev, void* stream) {
+  if (!c) return -1;
+  if (!hit_dev || !miss_dev || !label_dev || !goal_dev) return fail(c, -1, "null hit / miss / label / goal buffer");
+  TRY(check_aligned(c, {hit_dev, miss_dev, label_dev, goal_dev, region_dev, count_dev}, "hit / miss / label / goal / region / count buffer"));
+  TRY(check_cell_grid(c, nx, ny, SMJ_FRONT_MAX_SIDE, SMJ_FRONT_MAX_CELLS));
+  if (min_hits < 1) return fail(c, -1, "min_hits %d below 1: every cell would be occupied", min_hits);
+  if (lethal < 1 || lethal > 256) return fail(c, -1, "lethal %d outside [1, 256]: below 1 no cell is passable, above 256 means 256", lethal);
+  if (min_size < 1) return fail(c, -1, "min_size %d below 1: a region has at least one cell", min_size);
+  if (max_regions < 1 || max_regions > SMJ_FRONT_MAX_REGIONS) return fail(c, -1, "max_regions %d outside [1, %d]", max_regions, (int)SMJ_FRONT_MAX_REGIONS);
+  // the workgroup of an env reads its inputs while it stores (the labels of a large grid are built in place)
+  const uintptr_t cells = (uintptr_t)c->num_envs * (uintptr_t)nx * (uintptr_t)ny, rows = (uintptr_t)c->num_envs * (uintptr_t)max_regions;
+  TRY(check_disjoint(c, {{hit_dev, cells * 4u, "hit"}, {miss_dev, cells * 4u, "miss"}, {cost_dev, cells, "cost"}},
+                     {{label_dev, cells * 4u, "label"}, {goal_dev, rows * 4u, "goal"}, {region_dev, rows * 16u, "region"},
+                      {count_dev, (uintptr_t)c->num_envs * 8u, "count"}}));
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_front(c->num_envs, (const int*)hit_dev, (const int*)miss_dev, (const uint8_t*)cost_dev, nx, ny, min_hits, lethal, min_size, max_regions,
+                   (int*)label_dev, (int*)goal_dev, (int*)region_dev, (int*)count_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

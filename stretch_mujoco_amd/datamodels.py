@@ -244,6 +244,59 @@ def cells_of_points(points, origin, cell, ny, nx):
 
 
 @dataclass
+class StatusStretchFrontiers:
+    """New, without a reference counterpart: the frontier regions of pull_frontiers() (smj_occupancy_to_frontiers) over a grid laid
+    out as StatusStretchOccupancyGrid's -- the free cells that border unseen space, grouped into 8-connected regions, the largest
+    first.  Exact integers; the helpers turn them into metres and masks in torch.  `goal` is what pull_navigation_field takes as
+    its goal.  Device tensors, simulator-owned, not synchronised to the host."""
+    time: Any
+    goal: Any           # [B, G] int32: per kept region its representative cell (the region's cell nearest its centroid) as a linear index iy nx + ix; -1 = unused
+    label: Any          # [B, ny, nx] int32: the smallest linear index of the cell's region, -1 off the frontier (small regions are labelled too)
+    region: Any         # [B, G, 4] int32: label, size, sum of x, sum of y per kept region; -1, 0, 0, 0 on unused rows
+    count: Any          # [B, 2] int32: regions of at least min_size cells (may exceed G), frontier cells
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "base" or "world" ("grid" for a bare tensor)
+
+    def size(self):
+        """int32 [B, G]: the cells per kept region, 0 on unused rows."""
+        return self.region[..., 1]
+
+    def centroid(self):
+        """fp32 [B, G, 2]: the regions' centroids (x, y) in metres, origin + (sum / size + 0.5) cell; NaN on unused rows.  The
+        centroid of a curved frontier need not be free: drive to goal_xy()."""
+        import torch
+
+        size = self.region[..., 1:2].to(torch.float32)
+        o = torch.tensor([float(self.origin[0]), float(self.origin[1])], dtype=torch.float32, device=self.region.device)
+        xy = o + (self.region[..., 2:4].to(torch.float32) / size + 0.5) * float(self.cell)      # 0 / 0 on an unused row
+        return torch.where(size > 0, xy, torch.full_like(xy, float("nan")))
+
+    def goal_xy(self):
+        """fp32 [B, G, 2]: the centres (x, y) of the goal cells in metres; NaN where the goal is -1."""
+        import torch
+
+        nx = self.label.shape[-1]
+        g = self.goal.clamp(min=0)
+        ij = torch.stack((g % nx, torch.div(g, nx, rounding_mode="floor")), -1).to(torch.float32)
+        o = torch.tensor([float(self.origin[0]), float(self.origin[1])], dtype=torch.float32, device=self.goal.device)
+        xy = o + (ij + 0.5) * float(self.cell)
+        return torch.where((self.goal >= 0).unsqueeze(-1), xy, torch.full_like(xy, float("nan")))
+
+    def mask(self):
+        """bool [B, ny, nx]: the cells of the kept, reported regions (those with a row in `region`)."""
+        import torch
+
+        B, ny, nx = self.label.shape
+        kept = torch.zeros(B, ny * nx + 1, dtype=torch.bool, device=self.label.device)      # the last slot takes the unused rows
+        rows = self.region[..., 0].to(torch.int64)
+        kept.scatter_(1, torch.where(rows >= 0, rows, torch.full_like(rows, ny * nx)), True)
+        kept[:, ny * nx] = False
+        flat = self.label.reshape(B, ny * nx).to(torch.int64)
+        return (kept.gather(1, flat.clamp(min=0)) & (flat >= 0)).view(B, ny, nx)
+
+
+@dataclass
 class StatusStretchNavigationField:
     """New, without a reference counterpart: the exact cost-to-goal field of pull_navigation_field() (smj_costmap_to_navigation) over
     a grid laid out as StatusStretchOccupancyGrid's.  `potential` and `next` are exact integers; the helpers turn them into metres,

@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
+from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -145,6 +145,7 @@ class StretchBatchSimulator:
         self._hmaps = {}            # (frame, (ny, nx)) -> the simulator-owned (height, count) of pull_height_map
         self._occ = {}              # (frame, (ny, nx)) -> the simulator-owned (hit, miss) of pull_occupancy_grid
         self._nav = {}              # (ny, nx, G) -> the simulator-owned [potential, next or None, goal] of pull_navigation_field
+        self._front = {}            # (ny, nx, G) -> the simulator-owned [label, goal, region, count, hit, miss] of pull_frontiers
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
@@ -680,6 +681,79 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_costmap_to_navigation")
         return StatusStretchNavigationField(time=self._time(), potential=bufs[0], next=nxt, goal=bufs[2], origin=x0y0, cell=cell,
                                             frame=frame, neutral=neutral)
+
+    @_require_connection
+    def pull_frontiers(self, grid=None, *, min_hits: int = 1, min_size: int = 4, max_regions: int = 16, cost=None, lethal: int = 253,
+                       cell=None, origin=None, **occupancy_kwargs) -> StatusStretchFrontiers:
+        """Frontier regions of an occupancy grid in one HIP pass (smj_occupancy_to_frontiers, include/smj_frontier.h): the free
+        cells with an unseen 4-neighbour, grouped into 8-connected regions (`label`), and for the max_regions largest regions of at
+        least min_size cells a goal cell each (`goal`: the region's cell nearest its centroid), their sizes and coordinate sums
+        (`region`) and the totals (`count`).  Integers only: two calls give identical tensors.  New, without a reference
+        counterpart.  fr.goal is the goal of pull_navigation_field(fr.goal, cost): exploration without leaving the device.
+
+        grid: None -- pull_occupancy_grid(**occupancy_kwargs) is called; a StatusStretchOccupancyGrid (a world-frame map
+        accumulated over steps, say), whose frame, origin and cell are taken over; or an int8 tensor [B, ny, nx] in the convention
+        of occupancy() (> 0 occupied, 0 free, < 0 unknown) -- then cell and origin are these keywords (1.0 and (0, 0) if absent),
+        min_hits is 1 and the frame is "grid".
+        A cell is occupied when hit >= min_hits, else free when miss > 0, else unknown.
+        cost: None or a uint8 tensor [B, ny, nx], e.g. the df.inflated_cost(..) handed to pull_navigation_field: a frontier cell
+        must then have cost < lethal (1 .. 256), so that no goal lies where the robot does not fit.
+        1 <= min_size, 1 <= max_regions <= 64.  The tensors are simulator-owned and overwritten by the next call with the same
+        (shape, max_regions)."""
+        min_hits, min_size, G, lethal = int(min_hits), int(min_size), int(max_regions), int(lethal)
+        if min_hits < 1:
+            raise ValueError("min_hits must be >= 1")
+        if not 1 <= min_size < 1 << 31:
+            raise ValueError("min_size must be >= 1")
+        if not 1 <= G <= 64:
+            raise ValueError("max_regions must be in [1, 64]")
+        if not 1 <= lethal <= 256:
+            raise ValueError("lethal must be in [1, 256]")
+        B, dev = self.num_envs, self.device
+        if cost is not None and (not isinstance(cost, torch.Tensor) or cost.dtype != torch.uint8 or cost.dim() != 3 or cost.shape[0] != B):
+            raise ValueError(f"cost: None or a uint8 tensor [num_envs = {B}, ny, nx]")
+        if grid is not None and not isinstance(grid, StatusStretchOccupancyGrid):
+            if not isinstance(grid, torch.Tensor) or grid.dtype != torch.int8 or grid.dim() != 3 or grid.shape[0] != B:
+                raise ValueError(f"grid: None, a StatusStretchOccupancyGrid, or an int8 tensor [num_envs = {B}, ny, nx] as occupancy() gives")
+            if min_hits != 1:
+                raise ValueError("an occupancy() tensor has no counts: min_hits = 1")
+        self._upstream_kwargs(occupancy_kwargs, ("pull_occupancy_grid", "grid"), grid is None, cell, origin)
+        if grid is None:
+            grid = self.pull_occupancy_grid(**occupancy_kwargs)
+            cell = origin = None
+        states = None
+        if isinstance(grid, StatusStretchOccupancyGrid):
+            x0y0, cell = self._origin_cell(grid, origin, cell)
+            hit, miss, frame = grid.hit, grid.miss, grid.frame
+            for t in (hit, miss):
+                if (not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != B or t.dtype != torch.int32 or not t.is_contiguous()
+                        or t.device != dev or t.shape != hit.shape):
+                    raise ValueError(f"grid: contiguous int32 hit and miss [num_envs = {B}, ny, nx] on {dev}")
+            ny, nx = int(hit.shape[1]), int(hit.shape[2])
+        else:
+            x0y0, cell = self._origin_cell(None, origin, cell)
+            states, frame = grid, "grid"
+            ny, nx = int(grid.shape[1]), int(grid.shape[2])
+        self._check_cell_count("grid", ny, nx)
+        if cost is not None and tuple(cost.shape) != (B, ny, nx):
+            raise ValueError(f"cost: the grid's shape [{B}, {ny}, {nx}]")
+        new = lambda *shape: torch.empty(B, *shape, dtype=torch.int32, device=dev)
+        bufs = self._cached(self._front, (ny, nx, G), lambda: [new(ny, nx), new(G), new(G, 4), new(2), None, None])
+        if states is not None:
+            if bufs[4] is None:
+                bufs[4], bufs[5] = new(ny, nx), new(ny, nx)
+            states = states.to(dev)
+            bufs[4].copy_(states > 0)
+            bufs[5].copy_(states == 0)
+            hit, miss = bufs[4], bufs[5]
+        if cost is not None:
+            cost = cost.to(device=dev).contiguous()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = self._L.smj_occupancy_to_frontiers(self._ctx, vp(hit), vp(miss), vp(cost) if cost is not None else None, nx, ny, min_hits, lethal,
+                                                min_size, G, vp(bufs[0]), vp(bufs[1]), vp(bufs[2]), vp(bufs[3]), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_frontiers")
+        return StatusStretchFrontiers(time=self._time(), goal=bufs[1], label=bufs[0], region=bufs[2], count=bufs[3], origin=x0y0, cell=cell,
+                                      frame=frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

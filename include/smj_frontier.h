@@ -50,4 +50,5 @@ int smj_occupancy_to_frontiers(smj_ctx* ctx, const void* hit_dev, const void* mi
 #ifdef __cplusplus
 }
 #endif
+#include "smj_drive.h"
 #endif

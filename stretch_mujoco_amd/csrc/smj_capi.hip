@@ -28,6 +28,7 @@
 #include "smj_edt.h"
 #include "smj_nav.h"
 #include "smj_front.h"
+#include "smj_drive.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -832,6 +833,44 @@ int smj_occupancy_to_frontiers(smj_ctx* c, const void* hit_dev, const void* miss
   HIPCHK(c, hipSetDevice(c->device));
   smj_launch_front(c->num_envs, (const int*)hit_dev, (const int*)miss_dev, (const uint8_t*)cost_dev, nx, ny, min_hits, lethal, min_size, max_regions,
                    (int*)label_dev, (int*)goal_dev, (int*)region_dev, (int*)count_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static_assert((int)SMJ_DRIVE_NAV_NONE == SMJ_NAV_NONE && (int)SMJ_DRIVE_MAX_CELLS == (int)SMJ_NAV_MAX_CELLS && (int)SMJ_DRIVE_MAX_SIDE == (int)SMJ_NAV_MAX_SIDE,
+              "smj_drive.h reads the potential of smj_costmap_to_navigation");
+
+int smj_navigation_to_velocity(smj_ctx* c, const void* pose_dev, const void* twist_dev, const void* cost_dev, const void* potential_dev, int nx, int ny,
+                               float x0, float y0, float cell, const void* command_dev, const void* point_dev, const void* bias_dev, int num_candidates,
+                               int num_points, int lethal, int outside_is_free, int goal_weight, int obstacle_weight, int arrive_potential, float max_dv,
+                               float max_dw, void* cmd_dev, void* best_dev, void* score_dev, void* cell_dev, void* stream) {
+  if (!c) return -1;
+  if (!pose_dev || !potential_dev || !command_dev || !point_dev || !cmd_dev || !best_dev)
+    return fail(c, -1, "null pose / potential / command / point / cmd / best buffer");
+  TRY(check_aligned(c, {pose_dev, twist_dev, potential_dev, command_dev, point_dev, bias_dev, cmd_dev, best_dev, score_dev, cell_dev},
+                    "pose / twist / potential / command / point / bias / cmd / best / score / cell buffer"));
+  if ((uintptr_t)score_dev & 7) return fail(c, -1, "score buffer not aligned to 8 bytes");
+  TRY(check_cell_grid(c, nx, ny, SMJ_DRIVE_MAX_SIDE, SMJ_DRIVE_MAX_CELLS));
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (num_candidates < 1 || num_candidates > SMJ_DRIVE_MAX_CANDIDATES || num_points < 1 || num_points > SMJ_DRIVE_MAX_POINTS ||
+      num_candidates * num_points > SMJ_DRIVE_MAX_TABLE)
+    return fail(c, -1, "bad table %d x %d (1 <= num_candidates <= %d, 1 <= num_points <= %d, their product <= %d)", num_candidates, num_points,
+                (int)SMJ_DRIVE_MAX_CANDIDATES, (int)SMJ_DRIVE_MAX_POINTS, (int)SMJ_DRIVE_MAX_TABLE);
+  if (lethal < 1 || lethal > 256) return fail(c, -1, "lethal %d outside [1, 256]: below 1 every cell blocks, above 256 means 256", lethal);
+  if (goal_weight < 0 || goal_weight > SMJ_DRIVE_MAX_WEIGHT || obstacle_weight < 0 || obstacle_weight > SMJ_DRIVE_MAX_WEIGHT)
+    return fail(c, -1, "goal_weight %d or obstacle_weight %d outside [0, %d]", goal_weight, obstacle_weight, (int)SMJ_DRIVE_MAX_WEIGHT);
+  if (arrive_potential < 0 || arrive_potential >= SMJ_NAV_NONE) return fail(c, -1, "arrive_potential %d outside [0, SMJ_NAV_NONE)", arrive_potential);
+  if (!(max_dv >= 0.f && max_dw >= 0.f)) return fail(c, -1, "max_dv and max_dw must be >= 0 (+inf: no limit)");
+  const uintptr_t envs = (uintptr_t)c->num_envs, cells = envs * (uintptr_t)nx * (uintptr_t)ny, K = (uintptr_t)num_candidates, P = (uintptr_t)num_points;
+  TRY(check_disjoint(c, {{pose_dev, envs * 12u, "pose"}, {twist_dev, envs * 8u, "twist"}, {cost_dev, cells, "cost"}, {potential_dev, cells * 4u, "potential"},
+                         {command_dev, K * 8u, "command"}, {point_dev, K * P * 8u, "point"}, {bias_dev, K * 4u, "bias"}},
+                     {{cmd_dev, envs * 8u, "cmd"}, {best_dev, envs * 8u, "best"}, {score_dev, envs * K * 8u, "score"}, {cell_dev, envs * K * P * 4u, "cell"}}));
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_drive(c->num_envs, (const float*)pose_dev, (const float*)twist_dev, (const uint8_t*)cost_dev, (const int*)potential_dev, nx, ny, x0, y0, cell,
+                   (const float*)command_dev, (const float*)point_dev, (const int*)bias_dev, num_candidates, num_points, lethal, outside_is_free != 0,
+                   goal_weight, obstacle_weight, arrive_potential, max_dv, max_dw, (float*)cmd_dev, (int*)best_dev, (long long*)score_dev, (int*)cell_dev,
+                   (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -297,6 +297,51 @@ class StatusStretchFrontiers:
 
 
 @dataclass
+class StatusStretchBaseCommand:
+    """New, without a reference counterpart: the base command of pull_base_command() (smj_navigation_to_velocity), the best of a
+    table of candidate arcs judged on a navigation field and its costmap.  `v` and `w` are what set_base_velocity takes.  Device
+    tensors, simulator-owned, not synchronised to the host."""
+    time: Any
+    cmd: Any            # [2, B] fp32: rows v [m/s] and w [rad/s]; the chosen candidate's command bit for bit, (0, 0) unless status is 0
+    best: Any           # [B, 2] int32: the chosen candidate (-1 unless status is 0) and the status
+    score: Any          # [B, K] int64 or None: every candidate's score, NO_SCORE for a blocked one
+    cells: Any          # [B, K, P] int32 or None: the linear cell iy nx + ix of every point of the table, -1 outside the grid
+    frame: str          # the navigation field's: "base", "world" or "grid"
+
+    OK, ARRIVED, BLOCKED, OFF_GRID = 0, 1, 2, 3      # SMJ_DRIVE_*
+    NO_SCORE = (1 << 63) - 1                          # SMJ_DRIVE_NO_SCORE
+
+    @property
+    def v(self):
+        """fp32 [B]: a view of cmd's first row."""
+        return self.cmd[0]
+
+    @property
+    def w(self):
+        """fp32 [B]: a view of cmd's second row."""
+        return self.cmd[1]
+
+    @property
+    def chosen(self):
+        """int32 [B]: the chosen candidate's index, -1 unless status is 0."""
+        return self.best[:, 0]
+
+    @property
+    def status(self):
+        """int32 [B]: 0 ok, 1 arrived, 2 every candidate blocked, 3 the robot is off the grid or its pose is not finite."""
+        return self.best[:, 1]
+
+    def ok(self):
+        return self.best[:, 1] == self.OK
+
+    def arrived(self):
+        return self.best[:, 1] == self.ARRIVED
+
+    def blocked(self):
+        return self.best[:, 1] == self.BLOCKED
+
+
+@dataclass
 class StatusStretchNavigationField:
     """New, without a reference counterpart: the exact cost-to-goal field of pull_navigation_field() (smj_costmap_to_navigation) over
     a grid laid out as StatusStretchOccupancyGrid's.  `potential` and `next` are exact integers; the helpers turn them into metres,

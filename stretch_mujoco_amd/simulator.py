@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchCameras, StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
+from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -146,6 +146,8 @@ class StretchBatchSimulator:
         self._occ = {}              # (frame, (ny, nx)) -> the simulator-owned (hit, miss) of pull_occupancy_grid
         self._nav = {}              # (ny, nx, G) -> the simulator-owned [potential, next or None, goal] of pull_navigation_field
         self._front = {}            # (ny, nx, G) -> the simulator-owned [label, goal, region, count, hit, miss] of pull_frontiers
+        self._drive = {}            # (K, P, ny, nx) -> the simulator-owned cmd, best, score, cells, twist and pose of pull_base_command
+        self._drive_default = None  # arc_candidates() on the device, made by the first pull_base_command without a table
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
@@ -754,6 +756,130 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_frontiers")
         return StatusStretchFrontiers(time=self._time(), goal=bufs[1], label=bufs[0], region=bufs[2], count=bufs[3], origin=x0y0, cell=cell,
                                       frame=frame)
+
+    @_require_connection
+    def pull_base_command(self, nav, cost=None, *, candidates=None, lethal: int = 253, goal_weight: int = 1, obstacle_weight: int = 20,
+                          arrive_radius: float = 0.10, twist=None, max_accel=None, period=None, outside_is_free: bool = False, pose=None,
+                          scores: bool = False, cells: bool = False) -> StatusStretchBaseCommand:
+        """The base command that follows a navigation field, in one HIP pass (smj_navigation_to_velocity, include/smj_drive.h): a
+        trajectory-rollout local planner.  Per env every candidate arc of a table is laid over the grid from the robot's pose; arcs
+        that touch a cell with cost >= lethal (or leave the grid, unless outside_is_free), whose scoring point has no path to the
+        goal, or that the base cannot reach from its current velocity are dropped; the rest are scored
+        goal_weight * potential[scoring point] + obstacle_weight * (largest swept cost) + bias, and the smallest score wins, the
+        smallest index among equal ones.  Everything after the points have their cells is integers: two calls give identical
+        tensors.  cmd.v and cmd.w go into set_base_velocity as they are; nothing is read back to the host.  New, without a
+        reference counterpart.
+
+        nav: a StatusStretchNavigationField, whose frame, origin and cell are taken over.  cost: None (0 everywhere) or the uint8
+        tensor [B, ny, nx] the field was planned on.  The pose: sim.base_pose for a "world" field, zero for a "base" one (the grid
+        moves with the robot); pose= ([3, B] float: x, y, theta in the grid's frame) replaces either and is required for "grid".
+        candidates: a utils.BaseCandidates (utils.arc_candidates(...)); None is arc_candidates() with its defaults.
+        Status per env (cmd.status): 0 ok; 1 arrived -- potential at the robot's cell <= floor(arrive_radius / cell) * 10 * neutral,
+        i.e. about arrive_radius of path left; 2 every candidate dropped; 3 the robot is off the grid.  v = w = 0 unless 0.
+        max_accel = (a_v, a_w) with period [s]: only candidates within a_v * period, a_w * period of the current velocity are
+        kept; that velocity is twist ([2, B] float) or, by default, the last one commanded through set_base_velocity.
+        scores, cells: also return every candidate's score [B, K] and every point's cell [B, K, P].
+        The weights: with neutral 50 a cell of path costs 500, so a swept cost of 252 trades against about ten cells of detour.
+        The tensors are simulator-owned and overwritten by the next call with the same (K, P, shape)."""
+        from .utils import BaseCandidates, arc_candidates
+
+        B, dev = self.num_envs, self.device
+        if not isinstance(nav, StatusStretchNavigationField):
+            raise ValueError("nav: the StatusStretchNavigationField of pull_navigation_field()")
+        pot = nav.potential
+        if (not isinstance(pot, torch.Tensor) or pot.dim() != 3 or pot.shape[0] != B or pot.dtype != torch.int32 or not pot.is_contiguous()
+                or pot.device != dev):
+            raise ValueError(f"nav: a contiguous int32 potential [num_envs = {B}, ny, nx] on {dev}")
+        ny, nx = int(pot.shape[1]), int(pot.shape[2])
+        self._check_cell_count("nav", ny, nx)
+        x0y0, cell = self._origin_cell(nav, None, None)
+        if cost is not None and (not isinstance(cost, torch.Tensor) or cost.dtype != torch.uint8 or tuple(cost.shape) != (B, ny, nx)):
+            raise ValueError(f"cost: None or a uint8 tensor of the field's shape [{B}, {ny}, {nx}]")
+        lethal, goal_weight, obstacle_weight = int(lethal), int(goal_weight), int(obstacle_weight)
+        if not 1 <= lethal <= 256:
+            raise ValueError("lethal must be in [1, 256]")
+        if not (0 <= goal_weight <= 65535 and 0 <= obstacle_weight <= 65535):
+            raise ValueError("goal_weight and obstacle_weight must be in [0, 65535]")
+        arrive_radius = float(arrive_radius)
+        if not (np.isfinite(arrive_radius) and arrive_radius >= 0):
+            raise ValueError("arrive_radius must be finite and >= 0")
+        arrive = int(np.floor(arrive_radius / cell)) * 10 * int(nav.neutral)
+        if not 0 <= arrive < _lib.NAV_NONE:
+            raise ValueError("arrive_radius: more cells than a potential can hold")
+        if candidates is not None and not isinstance(candidates, BaseCandidates):
+            raise ValueError("candidates: None or the BaseCandidates of utils.arc_candidates()")
+        if candidates is None:
+            if self._drive_default is None:
+                self._drive_default = arc_candidates(device=dev)
+            candidates = self._drive_default
+        command, points, bias = candidates
+        if (not isinstance(command, torch.Tensor) or not isinstance(points, torch.Tensor) or command.dtype != torch.float32 or points.dtype != torch.float32
+                or command.dim() != 2 or command.shape[1] != 2 or points.dim() != 3 or points.shape[0] != command.shape[0] or points.shape[2] != 2):
+            raise ValueError("candidates: command fp32 [K, 2] and points fp32 [K, P, 2]")
+        K, P = int(points.shape[0]), int(points.shape[1])
+        if not (1 <= K <= 1024 and 1 <= P <= 256 and K * P <= 32768):
+            raise ValueError("candidates: 1 <= K <= 1024, 1 <= P <= 256 and K P <= 32768")
+        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.int32 or tuple(bias.shape) != (K,)):
+            raise ValueError(f"candidates: bias None or int32 [K = {K}]")
+        if nav.frame not in ("world", "base", "grid"):
+            raise ValueError('nav.frame must be "world", "base" or "grid"')
+        if pose is None and nav.frame == "grid":
+            raise ValueError('a "grid" field has no pose of its own: pose = [3, B] (x, y, theta in the grid\'s frame)')
+        if pose is not None and (not isinstance(pose, torch.Tensor) or not pose.is_floating_point() or tuple(pose.shape) != (3, B)):
+            raise ValueError(f"pose: a float tensor [3, num_envs = {B}]")
+        max_dv = max_dw = float("inf")
+        if max_accel is None:
+            if twist is not None or period is not None:
+                raise ValueError("twist and period belong to the dynamic window: give max_accel = (a_v, a_w) and period")
+        else:
+            try:
+                a_v, a_w = (float(q) for q in max_accel)
+                period = float(period)
+            except (TypeError, ValueError):
+                raise ValueError("max_accel = (a_v, a_w) with period in seconds") from None
+            if not (a_v >= 0 and a_w >= 0 and np.isfinite(period) and period > 0):
+                raise ValueError("max_accel >= 0, period > 0 and finite")
+            max_dv, max_dw = a_v * period, a_w * period
+            if twist is not None and (not isinstance(twist, torch.Tensor) or not twist.is_floating_point() or tuple(twist.shape) != (2, B)):
+                raise ValueError(f"twist: None or a float tensor [2, num_envs = {B}]")
+        new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
+        bufs = self._cached(self._drive, (K, P, ny, nx), lambda: dict(cmd=new(torch.float32, 2, B), best=new(torch.int32, B, 2), score=None, cells=None,
+                                                                       twist=None, pose=None))
+        if scores and bufs["score"] is None:
+            bufs["score"] = new(torch.int64, B, K)
+        if cells and bufs["cells"] is None:
+            bufs["cells"] = new(torch.int32, B, K, P)
+        if pose is not None or nav.frame == "base":
+            if bufs["pose"] is None:
+                bufs["pose"] = torch.zeros(3, B, dtype=torch.float32, device=dev)
+            if pose is not None:
+                bufs["pose"].copy_(pose)
+            else:
+                bufs["pose"].zero_()
+            pose_t = bufs["pose"]
+        else:
+            pose_t = self.base_pose
+        twist_t = None
+        if max_accel is not None:
+            if bufs["twist"] is None:
+                bufs["twist"] = new(torch.float32, 2, B)
+            twist_t = bufs["twist"]
+            if twist is not None:
+                twist_t.copy_(twist)
+            else:
+                twist_t[0].copy_(self.glue.bv_v)
+                twist_t[1].copy_(self.glue.bv_w)
+        if cost is not None:
+            cost = cost.to(device=dev).contiguous()
+        command, points = command.to(dev).contiguous(), points.to(dev).contiguous()
+        bias = bias.to(dev).contiguous() if bias is not None else None
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        score_t, cells_t = (bufs["score"] if scores else None), (bufs["cells"] if cells else None)
+        rc = self._L.smj_navigation_to_velocity(self._ctx, vp(pose_t), vp(twist_t), vp(cost), vp(pot), nx, ny, x0y0[0], x0y0[1], cell, vp(command), vp(points),
+                                                vp(bias), K, P, lethal, int(bool(outside_is_free)), goal_weight, obstacle_weight, arrive, max_dv, max_dw,
+                                                vp(bufs["cmd"]), vp(bufs["best"]), vp(score_t), vp(cells_t), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_navigation_to_velocity")
+        return StatusStretchBaseCommand(time=self._time(), cmd=bufs["cmd"], best=bufs["best"], score=score_t, cells=cells_t, frame=nav.frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

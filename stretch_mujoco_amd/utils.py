@@ -6,6 +6,7 @@ map_between_ranges (:352-360), compute_K (:56-61), limit_depth_distance (:87-91)
 from __future__ import annotations
 
 import math
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -86,3 +87,76 @@ def to_real_gripper_range(pos):
 def to_sim_gripper_range(pos):
     """stretch_mujoco/mujoco_server.py:580-588"""
     return map_between_ranges(pos, config.robot_settings["gripper_min_max"], config.robot_settings["sim_gripper_min_max"])
+
+
+class BaseCandidates(NamedTuple):
+    """The candidate table of pull_base_command() / smj_navigation_to_velocity, shared by all envs: fp32 tensors on one device."""
+    command: Any        # [K, 2]: the (v, w) a candidate stands for
+    points: Any         # [K, P, 2]: points in the robot's frame (x forward, y left); the first P - 1 are swept, the last one scores
+    bias: Any           # [K] int32 or None: added to the candidate's score
+
+
+def unicycle_pose(v, w, t):
+    """Pose (x, y, theta) of a unicycle that starts at the origin facing +x and drives (v, w) for t seconds, fp64, arrays alike:
+    (v/w sin(wt), v/w (1 - cos(wt)), wt), written as v t sinc(a) and v t (a/2) sinc(a/2)^2 with a = wt and sinc(a) = sin(a) / a,
+    which is the same closed form for every w and the straight line at w = 0: nothing blows up near it."""
+    v, w, t = (np.asarray(q, np.float64) for q in (v, w, t))
+    a = w * t
+    sinc = lambda z: np.sinc(z / np.pi)      # numpy's sinc is sin(pi z) / (pi z)
+    return v * t * sinc(a), v * t * 0.5 * a * sinc(0.5 * a) ** 2, a
+
+
+def arc_candidates(v=None, w=None, horizon: float = 1.5, samples: int = 12, lookahead: float = 0.3, footprint=None, bias=None, turn_bias: int = 0, device=None) -> BaseCandidates:
+    """Candidate arcs for pull_base_command(): for each pair (v[k], w[k]) the poses of the unicycle at t = horizon (i + 1) / samples,
+    i = 0 .. samples - 1, built in fp64 on the host (unicycle_pose) and stored as fp32 tensors on `device`.
+    footprint None: one swept point per sample, the pose's position -- the costmap's inflation stands for the body, as in
+    pull_navigation_field.  footprint [(x, y), ..] in the robot's frame: those points at every sample pose, sample after sample.
+    The scoring point lies `lookahead` metres ahead of the final pose along its heading.  So P = samples * F + 1.
+    v, w None: the default set, v in (0.25, 0.16, 0.08, 0) m/s by nine w evenly in [-1, 1] rad/s, without (0, 0): 35 candidates,
+    the fastest first, so that among equal scores the faster one wins.  bias: None or K integers; turn_bias is added to the bias of
+    the candidates with v = 0 (turning in place): with a scoring point ahead of the arc's end a robot that faces a goal closer than
+    that point would otherwise rather turn than drive the last stretch.
+    Limits of the entry: K <= 1024, P <= 256, K P <= 32768 (ValueError)."""
+    import torch
+
+    if (v is None) != (w is None):
+        raise ValueError("v and w: both None (the default set) or two sequences of equal length")
+    if v is None:
+        vs, ws = np.meshgrid(np.array([0.25, 0.16, 0.08, 0.0]), np.linspace(-1.0, 1.0, 9), indexing="ij")
+        keep = (vs != 0) | (ws != 0)
+        v, w = vs[keep], ws[keep]
+    v, w = np.atleast_1d(np.asarray(v, np.float64)), np.atleast_1d(np.asarray(w, np.float64))
+    samples = int(samples)
+    horizon, lookahead = float(horizon), float(lookahead)
+    if v.ndim != 1 or v.shape != w.shape or v.size < 1 or not (np.isfinite(v).all() and np.isfinite(w).all()):
+        raise ValueError("v and w: two finite sequences of equal length >= 1")
+    if samples < 1 or not (np.isfinite(horizon) and horizon > 0) or not np.isfinite(lookahead):
+        raise ValueError("samples >= 1, horizon > 0 and finite, lookahead finite")
+    if footprint is None:
+        fp = np.zeros((1, 2))
+    else:
+        fp = np.asarray(footprint, np.float64)
+        if fp.ndim != 2 or fp.shape[1] != 2 or fp.shape[0] < 1 or not np.isfinite(fp).all():
+            raise ValueError("footprint: None or [(x, y), ..] in the robot's frame, finite")
+    K, P = v.size, samples * fp.shape[0] + 1
+    if K > 1024 or P > 256 or K * P > 32768:
+        raise ValueError(f"{K} candidates of {P} points: K <= 1024, P <= 256 and K P <= 32768")
+    t = horizon * (np.arange(samples) + 1.0) / samples
+    x, y, th = unicycle_pose(v[:, None], w[:, None], t[None, :])                      # [K, samples]
+    c, s = np.cos(th)[..., None], np.sin(th)[..., None]
+    sx = x[..., None] + c * fp[:, 0] - s * fp[:, 1]                                     # [K, samples, F]
+    sy = y[..., None] + s * fp[:, 0] + c * fp[:, 1]
+    swept = np.stack((sx, sy), -1).reshape(K, P - 1, 2)
+    score = np.stack((x[:, -1] + lookahead * np.cos(th[:, -1]), y[:, -1] + lookahead * np.sin(th[:, -1])), -1)
+    points = np.concatenate((swept, score[:, None, :]), 1)
+    turn_bias = int(turn_bias)
+    if bias is not None or turn_bias:
+        b = np.zeros(K, np.int64) if bias is None else np.asarray(bias)
+        if b.shape != (K,) or not np.issubdtype(b.dtype, np.integer):
+            raise ValueError(f"bias: None or {K} int32 values")
+        b = b.astype(np.int64) + turn_bias * (v == 0)
+        if np.abs(b).max(initial=0) >= 1 << 31:
+            raise ValueError(f"bias: None or {K} int32 values")
+        bias = torch.tensor(b.astype(np.int32), dtype=torch.int32, device=device)
+    return BaseCandidates(command=torch.tensor(np.stack((v, w), 1), dtype=torch.float32, device=device),
+                          points=torch.tensor(points, dtype=torch.float32, device=device), bias=bias)

@@ -79,4 +79,5 @@ int smj_navigation_to_velocity(smj_ctx* ctx, const void* pose_dev, const void* t
 #ifdef __cplusplus
 }
 #endif
+#include "smj_scanmatch.h"
 #endif

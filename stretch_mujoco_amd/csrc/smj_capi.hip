@@ -29,6 +29,7 @@
 #include "smj_nav.h"
 #include "smj_front.h"
 #include "smj_drive.h"
+#include "smj_match.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -871,6 +872,52 @@ int smj_navigation_to_velocity(smj_ctx* c, const void* pose_dev, const void* twi
                    (const float*)command_dev, (const float*)point_dev, (const int*)bias_dev, num_candidates, num_points, lethal, outside_is_free != 0,
                    goal_weight, obstacle_weight, arrive_potential, max_dv, max_dw, (float*)cmd_dev, (int*)best_dev, (long long*)score_dev, (int*)cell_dev,
                    (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static_assert((int)SMJ_MATCH_MAX_CELLS == (int)SMJ_OCC_MAX_CELLS && (int)SMJ_MATCH_MAX_CELLS == (int)SMJ_EDT_MAX_CELLS && (int)SMJ_MATCH_MAX_SIDE == (int)SMJ_EDT_MAX_SIDE,
+              "smj_match.h matches scans against the maps of smj_lidar_to_occupancy and smj_occupancy_to_distance");
+
+int smj_scan_to_pose(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame, float r_min, float r_max, const void* field_dev, int nx, int ny, float x0,
+                     float y0, float cell, const void* pose_dev, const void* angle_dev, const void* angle_bias_dev, int num_angles, int wx, int wy,
+                     int shift_weight, int min_points, void* pose_out_dev, void* best_dev, void* score_dev, void* cell_dev, void* stream) {
+  if (!c) return -1;
+  FrameKind fk;
+  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to match");
+  if (!lidar_dev || !field_dev || !pose_dev || !angle_dev || !pose_out_dev || !best_dev)
+    return fail(c, -1, "null scan / field / pose / angle / pose_out / best buffer");
+  TRY(check_aligned(c, {lidar_dev, pose_dev, angle_dev, angle_bias_dev, pose_out_dev, best_dev, score_dev, cell_dev},
+                    "scan / pose / angle / angle_bias / pose_out / best / score / cell buffer"));
+  const int nlidar = c->render.nlidar;
+  if (nlidar > SMJ_MATCH_MAX_POINTS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MATCH_MAX_POINTS);
+  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_cell_grid(c, nx, ny, SMJ_MATCH_MAX_SIDE, SMJ_MATCH_MAX_CELLS));
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
+  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d, the bound of smj_lidar_to_occupancy", (int)SMJ_OCC_MAX_STEPS);
+  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
+  TRY(check_frame(c, frame, false, &fk));
+  if (num_angles < 1 || num_angles > SMJ_MATCH_MAX_ANGLES) return fail(c, -1, "num_angles %d outside [1, %d]", num_angles, (int)SMJ_MATCH_MAX_ANGLES);
+  if (wx < 0 || wx > SMJ_MATCH_MAX_WINDOW || wy < 0 || wy > SMJ_MATCH_MAX_WINDOW)
+    return fail(c, -1, "window %d x %d outside [0, %d]", wx, wy, (int)SMJ_MATCH_MAX_WINDOW);
+  if (shift_weight < 0 || shift_weight > SMJ_MATCH_MAX_SHIFT_WEIGHT) return fail(c, -1, "shift_weight %d outside [0, %d]", shift_weight, (int)SMJ_MATCH_MAX_SHIFT_WEIGHT);
+  if (min_points < 1 || min_points > SMJ_MATCH_MAX_POINTS) return fail(c, -1, "min_points %d outside [1, %d]", min_points, (int)SMJ_MATCH_MAX_POINTS);
+  // the workgroup of an env reads its inputs while others store
+  const uintptr_t envs = (uintptr_t)c->num_envs, T = (uintptr_t)num_angles, cand = T * (uintptr_t)(2 * wy + 1) * (uintptr_t)(2 * wx + 1);
+  const uintptr_t ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
+  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
+                         {pose_dev, envs * 12u, "pose"}, {angle_dev, T * 4u, "angle"}, {angle_bias_dev, T * 4u, "angle_bias"},
+                         {c->state.xpose, 12u * (uintptr_t)c->model.nbody_all * ld * 4u, "XPOSE slot's"}},
+                     {{pose_out_dev, envs * 12u, "pose_out"}, {best_dev, envs * 16u, "best"}, {score_dev, envs * cand * 4u, "score"},
+                      {cell_dev, envs * T * (uintptr_t)nlidar * 8u, "cell"}}));
+  TRY(check_xpose(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_match(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
+                   c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
+                   (const float*)pose_dev, (const float*)angle_dev, (const int*)angle_bias_dev, num_angles, wx, wy, shift_weight, min_points,
+                   (float*)pose_out_dev, (int*)best_dev, (int*)score_dev, (int*)cell_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

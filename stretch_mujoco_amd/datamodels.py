@@ -211,6 +211,19 @@ class StatusStretchDistanceField:
         cost = torch.where(d > r_inf, torch.zeros_like(cost), cost)
         return cost.to(torch.uint8)
 
+    def likelihood(self, sigma: float = 0.10):
+        """uint8 [B, ny, nx]: the likelihood field of pull_scan_match() -- what a scan point that lands in the cell is worth,
+        floor(255 exp(-d^2 / (2 sigma^2)) + 0.5) with d = sqrt(dist2) cell in metres (evaluated in fp64), 255 on an obstacle, 0 where
+        there is no obstacle in reach; sigma in metres."""
+        import torch
+
+        sigma = float(sigma)
+        if not (0 < sigma < float("inf")):
+            raise ValueError("likelihood: sigma in metres, finite and > 0")
+        k = float(self.cell) ** 2 / (2.0 * sigma * sigma)
+        field = torch.floor(255.0 * torch.exp(-k * self.dist2.to(torch.float64)) + 0.5)
+        return torch.where(self.dist2 >= self.NONE, torch.zeros_like(field), field).to(torch.uint8)
+
 
 def offsets_of_cells(index):
     """int32 [B, ny, nx, 2]: (dy, dx) in cells from each cell (iy, ix) of a grid [B, ny, nx] to the cell its entry names as a linear
@@ -339,6 +352,94 @@ class StatusStretchBaseCommand:
 
     def blocked(self):
         return self.best[:, 1] == self.BLOCKED
+
+
+@dataclass
+class StatusStretchScanMatch:
+    """New, without a reference counterpart: the pose estimate of pull_scan_match() (smj_scan_to_pose), the best of a window of
+    rotations and whole-cell shifts round a prior, judged by the sum of a likelihood field under the scan's returns.  `pose` is what
+    pull_base_command(pose=...) takes.  Device tensors, simulator-owned, not synchronised to the host."""
+    time: Any
+    pose: Any           # [3, B] fp32: rows x, y, theta in the field's frame; the winner's pose with status 0, the prior bit for bit otherwise
+    best: Any           # [B, 4] int32: the winner's index (-1 unless status is 0), its score J (0 unless status is 0), the counted returns n, the status
+    score: Any          # [B, T, 2 wy + 1, 2 wx + 1] int32 or None: J of every candidate
+    cells: Any          # [B, T, nlidar, 2] int32 or None: (ix, iy) of every ray and rotation, NO_CELL twice where it has none
+    angles: Any         # [T] fp32: the rotation offsets searched
+    window: Any         # (wx, wy): the shifts searched, in cells on either side
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "world" or "grid"
+    bias: Any = None    # [T] int32 or None: what a rotation costs (utils.scan_angles(weight=...))
+    shift_weight: int = 0
+
+    OK, FEW, OFF = 0, 1, 2      # SMJ_MATCH_*
+    NO_CELL = -32768            # SMJ_MATCH_NO_CELL
+
+    @property
+    def status(self):
+        """int32 [B]: 0 ok, 1 fewer returns than min_points, 2 the prior is not finite."""
+        return self.best[:, 3]
+
+    def ok(self):
+        return self.best[:, 3] == self.OK
+
+    def offset(self):
+        """int32 [B, 3]: (dx, dy, t) of the winner -- shifts in cells and the row of `angles` -- from its index; zeros unless ok()."""
+        import torch
+
+        wx, wy = self.window
+        i = self.best[:, 0].clamp(min=0)
+        row = torch.div(i, 2 * wx + 1, rounding_mode="floor")
+        off = torch.stack((i % (2 * wx + 1) - wx, row % (2 * wy + 1) - wy, torch.div(row, 2 * wy + 1, rounding_mode="floor")), 1)
+        return torch.where(self.ok().unsqueeze(1), off, torch.zeros_like(off)).to(torch.int32)
+
+    def fit(self):
+        """fp32 [B]: S / (255 n), the mean reward of a counted return at the winner, 1 for a scan that lies on the map's obstacles;
+        0 unless ok().  S is the winner's J with the rotation's bias and the shift's weight taken out again."""
+        import torch
+
+        off = self.offset().to(torch.int64)
+        S = self.best[:, 1].to(torch.int64) + int(self.shift_weight) * (off[:, 0] ** 2 + off[:, 1] ** 2)
+        if self.bias is not None:
+            S = S + self.bias.to(torch.int64).clamp(0, 1 << 20)[off[:, 2]]
+        n = self.best[:, 2].clamp(min=1).to(torch.float32)
+        return torch.where(self.ok(), S.to(torch.float32) / (255.0 * n), torch.zeros_like(n))
+
+    def refined(self):
+        """fp32 [3, B]: `pose` moved to the vertex of the parabola through the winner's J and its two neighbours' along each of x, y
+        (in cells) and theta (the neighbours in angle, whatever their rows in `angles`).  Along an axis on which the winner lies on
+        the border of the window, or whose three scores are no proper maximum, the winner itself stays; so do envs that are not
+        ok().  Needs pull_scan_match(scores=True)."""
+        import torch
+
+        if self.score is None:
+            raise ValueError("refined() needs pull_scan_match(scores=True)")
+        B, T, WY, WX = self.score.shape
+        off = self.offset().to(torch.int64)
+        ix, iy, t = off[:, 0] + self.window[0], off[:, 1] + self.window[1], off[:, 2]
+        J = self.score.to(torch.float64)
+        e = torch.arange(B, device=J.device)
+
+        def vertex(j0, j1, j2, a0, a1, a2, inner):
+            """The abscissa, relative to a1, of the vertex of the parabola through (a0, j0), (a1, j1), (a2, j2); 0 where not inner."""
+            u, v = a1 - a0, a1 - a2
+            num = u * u * (j1 - j2) - v * v * (j1 - j0)
+            den = u * (j1 - j2) - v * (j1 - j0)
+            good = inner & (den != 0) & (j1 >= j0) & (j1 >= j2)
+            return torch.where(good, -0.5 * num / torch.where(den != 0, den, torch.ones_like(den)), torch.zeros_like(num))
+
+        one = torch.ones(B, dtype=torch.float64, device=J.device)
+        xin, yin = (ix > 0) & (ix < WX - 1), (iy > 0) & (iy < WY - 1)
+        sx = vertex(J[e, t, iy, (ix - 1).clamp(min=0)], J[e, t, iy, ix], J[e, t, iy, (ix + 1).clamp(max=WX - 1)], -one, 0 * one, one, xin)
+        sy = vertex(J[e, t, (iy - 1).clamp(min=0), ix], J[e, t, iy, ix], J[e, t, (iy + 1).clamp(max=WY - 1), ix], -one, 0 * one, one, yin)
+        ang = self.angles.to(torch.float64)
+        order = torch.argsort(ang)
+        rank = torch.argsort(order)[t]                                   # the winner's place among the sorted angles
+        lo, hi = order[(rank - 1).clamp(min=0)], order[(rank + 1).clamp(max=T - 1)]
+        st = vertex(J[e, lo, iy, ix], J[e, t, iy, ix], J[e, hi, iy, ix], ang[lo], ang[t], ang[hi], (rank > 0) & (rank < T - 1))
+        ok = self.ok()
+        delta = torch.stack((sx * float(self.cell), sy * float(self.cell), st), 0)
+        return torch.where(ok.unsqueeze(0), (self.pose.to(torch.float64) + delta).to(torch.float32), self.pose)
 
 
 @dataclass

@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchSensors, cells_of_points
+from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchScanMatch, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -148,6 +148,8 @@ class StretchBatchSimulator:
         self._front = {}            # (ny, nx, G) -> the simulator-owned [label, goal, region, count, hit, miss] of pull_frontiers
         self._drive = {}            # (K, P, ny, nx) -> the simulator-owned cmd, best, score, cells, twist and pose of pull_base_command
         self._drive_default = None  # arc_candidates() on the device, made by the first pull_base_command without a table
+        self._match = {}            # (T, wx, wy, ny, nx) -> the simulator-owned pose, best, score, cells and prior of pull_scan_match
+        self._match_default = None  # scan_angles() on the device, made by the first pull_scan_match without a table
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
@@ -880,6 +882,124 @@ class StretchBatchSimulator:
                                                 vp(bufs["cmd"]), vp(bufs["best"]), vp(score_t), vp(cells_t), self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_navigation_to_velocity")
         return StatusStretchBaseCommand(time=self._time(), cmd=bufs["cmd"], best=bufs["best"], score=score_t, cells=cells_t, frame=nav.frame)
+
+    @_require_connection
+    def pull_scan_match(self, field, prior=None, *, sigma: float = 0.10, window=(0.5, 0.5), angles=None, range_limits=(0.2, 5.0),
+                        min_points: int = 30, shift_weight: int = 0, scores: bool = False, cells: bool = False, origin=None,
+                        cell=None) -> StatusStretchScanMatch:
+        """Where in a map the lidar scan of the last step was taken, in one HIP pass (smj_scan_to_pose, include/smj_scanmatch.h): a
+        correlative scan matcher.  Per env the scan's returns are laid over a likelihood field from every pose of a window round a
+        prior -- the rotations of a table by whole-cell shifts -- and the pose under which they collect the largest sum wins, the
+        smallest index among equal sums.  Everything after the points have their cells is integers: two calls give identical
+        tensors.  match.pose goes into pull_base_command(pose=...) as it is; nothing is read back to the host.  New, without a
+        reference counterpart: it stands where a user of the real robot runs AMCL or slam_toolbox.
+
+        field: a StatusStretchDistanceField (of a world-frame map, say), whose likelihood(sigma) is matched against and whose frame,
+        origin and cell are taken over; a StatusStretchOccupancyGrid, which goes through pull_distance_field() first (and so
+        overwrites that call's tensors); or a uint8 tensor [B, ny, nx], the reward of a point per cell, with origin= and cell=.
+        The frame is "world" or "grid"; a "base" grid moves with the robot and is no map (ValueError).
+        prior: [3, B] float (x, y, theta in the field's frame); None is sim.base_pose, the simulator's own.
+        window = (metres in x, metres in y) searched on either side of the prior, in whole cells: round(window / cell) <= 32 each.
+        angles: a utils.ScanAngles (utils.scan_angles(...)); None is scan_angles() with its defaults, 21 rotations.
+        range_limits = (r_min, r_max) as in pull_occupancy_grid: only ranges inside count.  Status per env (match.status): 0 ok;
+        1 fewer than min_points returns; 2 the prior is not finite.  The pose is the prior unless 0.
+        shift_weight: taken from a candidate's sum per squared cell of shift (0 .. 1024), to prefer the prior among near-equal poses.
+        scores, cells: also return every candidate's score [B, T, 2 wy + 1, 2 wx + 1] (refined() needs it) and every ray's cell.
+        Needs StretchSensors.base_lidar in sensors_to_use.
+        The tensors are simulator-owned and overwritten by the next call with the same (T, window, shape)."""
+        from .utils import ScanAngles, scan_angles
+
+        B, dev = self.num_envs, self.device
+        if not self._read_flags & _lib.READ_LIDAR:
+            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+        if self.nlidar > 1024:
+            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_pose takes 1024")
+        grid = None
+        if isinstance(field, (StatusStretchDistanceField, StatusStretchOccupancyGrid)):
+            src = field.dist2 if isinstance(field, StatusStretchDistanceField) else field.hit
+            if not isinstance(src, torch.Tensor) or src.dim() != 3 or src.shape[0] != B or src.dtype != torch.int32 or src.device != dev:
+                raise ValueError(f"field: int32 tensors [num_envs = {B}, ny, nx] on {dev}")
+            x0y0, cell = self._origin_cell(field, origin, cell)
+            frame, (ny, nx) = field.frame, (int(v) for v in src.shape[1:])
+            sigma = float(sigma)
+            if not (0 < sigma < float("inf")):
+                raise ValueError("sigma: metres, finite and > 0")
+            if isinstance(field, StatusStretchOccupancyGrid):
+                grid, field = field, None
+        else:
+            if not isinstance(field, torch.Tensor) or field.dtype != torch.uint8 or field.dim() != 3 or field.shape[0] != B:
+                raise ValueError(f"field: a StatusStretchDistanceField, a StatusStretchOccupancyGrid, or a uint8 tensor [num_envs = {B}, ny, nx]")
+            if origin is None or cell is None:
+                raise ValueError("a bare field needs origin = (x0, y0) and cell")
+            x0y0, cell = self._origin_cell(None, origin, cell)
+            frame, (ny, nx) = "grid", (int(v) for v in field.shape[1:])
+        if frame not in ("world", "grid"):
+            raise ValueError('the field\'s frame must be "world" or "grid": a "base" grid moves with the robot and is no map')
+        self._check_cell_count("field", ny, nx)
+        try:
+            r_min, r_max = (float(v) for v in range_limits)
+            wx, wy = (int(round(float(v) / cell)) for v in window)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("range_limits = (r_min, r_max), window = (metres in x, metres in y)") from None
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
+            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
+        if np.float32(r_max) / np.float32(cell) > 8192:
+            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        if not (0 <= wx <= 32 and 0 <= wy <= 32):
+            raise ValueError("window: 0 <= round(window / cell) <= 32 cells on either side")
+        min_points, shift_weight = int(min_points), int(shift_weight)
+        if not 1 <= min_points <= 1024:
+            raise ValueError("min_points must be in [1, 1024]")
+        if not 0 <= shift_weight <= 1024:
+            raise ValueError("shift_weight must be in [0, 1024]")
+        if angles is not None and not isinstance(angles, ScanAngles):
+            raise ValueError("angles: None or the ScanAngles of utils.scan_angles()")
+        if angles is None:
+            if self._match_default is None:
+                self._match_default = scan_angles(device=dev)
+            angles = self._match_default
+        ang, bias = angles
+        if not isinstance(ang, torch.Tensor) or ang.dtype != torch.float32 or ang.dim() != 1 or not 1 <= ang.shape[0] <= 64:
+            raise ValueError("angles: fp32 [T], 1 <= T <= 64")
+        T = int(ang.shape[0])
+        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.int32 or tuple(bias.shape) != (T,)):
+            raise ValueError(f"angles: bias None or int32 [T = {T}]")
+        if prior is not None and (not isinstance(prior, torch.Tensor) or not prior.is_floating_point() or tuple(prior.shape) != (3, B)):
+            raise ValueError(f"prior: None or a float tensor [3, num_envs = {B}]")
+        body, offset = self._base_frame()
+        if offset is not None:
+            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's points cannot be formed in "
+                             "the robot's frame")
+        # every ValueError has been raised: from here on the device works
+        if grid is not None:
+            field = self.pull_distance_field(grid)
+        if isinstance(field, StatusStretchDistanceField):
+            field = field.likelihood(sigma)
+        field = field.to(device=dev).contiguous()
+        new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
+        bufs = self._cached(self._match, (T, wx, wy, ny, nx), lambda: dict(pose=new(torch.float32, 3, B), best=new(torch.int32, B, 4), score=None,
+                                                                            cells=None, prior=None))
+        if scores and bufs["score"] is None:
+            bufs["score"] = new(torch.int32, B, T, 2 * wy + 1, 2 * wx + 1)
+        if cells and bufs["cells"] is None:
+            bufs["cells"] = new(torch.int32, B, T, self.nlidar, 2)
+        if prior is not None:
+            if bufs["prior"] is None:
+                bufs["prior"] = new(torch.float32, 3, B)
+            bufs["prior"].copy_(prior)
+            prior_t = bufs["prior"]
+        else:
+            prior_t = self.base_pose
+        ang = ang.to(dev).contiguous()
+        bias = bias.to(dev).contiguous() if bias is not None else None
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        score_t, cells_t = (bufs["score"] if scores else None), (bufs["cells"] if cells else None)
+        rc = self._L.smj_scan_to_pose(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(field), nx, ny, x0y0[0], x0y0[1], cell, vp(prior_t), vp(ang),
+                                      vp(bias), T, wx, wy, shift_weight, min_points, vp(bufs["pose"]), vp(bufs["best"]), vp(score_t), vp(cells_t),
+                                      self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_scan_to_pose")
+        return StatusStretchScanMatch(time=self._time(), pose=bufs["pose"], best=bufs["best"], score=score_t, cells=cells_t, angles=ang,
+                                      window=(wx, wy), origin=x0y0, cell=cell, frame=frame, bias=bias, shift_weight=shift_weight)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

@@ -96,6 +96,33 @@ class BaseCandidates(NamedTuple):
     bias: Any           # [K] int32 or None: added to the candidate's score
 
 
+class ScanAngles(NamedTuple):
+    """The rotation table of pull_scan_match() / smj_scan_to_pose, shared by all envs: tensors on one device."""
+    angles: Any         # [T] fp32: offsets added to the prior's theta [rad]
+    bias: Any           # [T] int32: taken from the score of every candidate with that rotation
+
+
+def scan_angles(window: float = 0.1745, step: float = 0.008727, weight: int = 0, device=None) -> ScanAngles:
+    """Rotation offsets for pull_scan_match(): k step for k = 0, -1, +1, -2, +2, .. out to n = round(window / (2 step)) steps on
+    either side, so `window` is the whole width searched [rad] and T = 2 n + 1 (the defaults: 10 degrees in steps of half a degree,
+    T = 21).  In this order the entry's tie-break -- the smallest index among equal scores -- prefers the smaller rotation.
+    bias = weight |k|: what a rotation of k steps costs, in units of the field (255 per scan point on an obstacle).
+    Limits of the entry: T <= 64, bias <= 2^20 (ValueError)."""
+    import torch
+
+    window, step, weight = float(window), float(step), int(weight)
+    if not (np.isfinite(window) and window >= 0 and np.isfinite(step) and step > 0):
+        raise ValueError("window >= 0 and step > 0, both finite [rad]")
+    n = int(round(window / (2.0 * step)))
+    if 2 * n + 1 > 64:
+        raise ValueError(f"{2 * n + 1} rotations: T <= 64 (a wider step, or a narrower window)")
+    if weight < 0 or weight * n > 1 << 20:
+        raise ValueError("weight >= 0 and weight * n <= 2^20")
+    k = np.array([0] + [s * j for j in range(1, n + 1) for s in (-1, 1)], np.int64)
+    return ScanAngles(angles=torch.tensor(k * step, dtype=torch.float32, device=device),
+                      bias=torch.tensor(weight * np.abs(k), dtype=torch.int32, device=device))
+
+
 def unicycle_pose(v, w, t):
     """Pose (x, y, theta) of a unicycle that starts at the origin facing +x and drives (v, w) for t seconds, fp64, arrays alike:
     (v/w sin(wt), v/w (1 - cos(wt)), wt), written as v t sinc(a) and v t (a/2) sinc(a/2)^2 with a = wt and sinc(a) = sin(a) / a,

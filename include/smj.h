@@ -95,7 +95,13 @@ enum {
 int smj_create(const void* blob, size_t nbytes, int num_envs, int device, smj_ctx** out);
 int smj_destroy(smj_ctx* ctx);
 
-/* Attach a caller-owned device buffer to a slot (the MjData field views the reference reads/writes). */
+/* Attach a caller-owned device buffer to a slot (the MjData field views the reference reads/writes).  `ld` is the distance in 4-byte words
+ * between two rows of a batch-major slot (between nothing for SMJ_SLOT_NSTEP, whose one row may carry any ld >= num_envs; unused for the
+ * env-major SMJ_SLOT_CONTACTS); ld < num_envs is refused with -1 and leaves the slot as it was.  The library reads and writes the words
+ * [row][0 .. num_envs-1] of a slot and no others: the columns num_envs .. ld-1 stay the caller's (a padded or sliced tensor).  Rows need no
+ * alignment beyond 4 bytes.  ALL batch-major slots bound at the time of a call must carry ONE ld: smj_step, smj_reset and
+ * smj_base_controller_tick return -5 otherwise and touch nothing.  A slot may be re-bound (or unbound with a null pointer) between calls;
+ * the next call uses the new buffer, the old one is not touched again. */
 int smj_bind(smj_ctx* ctx, int slot, void* dev_ptr, long ld);
 
 /* Copy of model constants the host glue needs: qpos0[nq], key_ctrl[nkey][nu], jnt ranges are read from the blob
@@ -111,7 +117,9 @@ int smj_reset(smj_ctx* ctx, const uint8_t* mask_dev, void* stream);
  * On return (stream order) the bound ACT_LENGTH / ACT_VELOCITY / BASE_POSE hold what MjData holds after the last mj_step --
  * the values of its forward pass, one step behind qpos, exactly what pull_status reads (mujoco_server.py:465-515) -- and,
  * if requested in read_flags, GYRO/ACCEL (+ LIDAR) hold the sensor values of the last step and CONTACTS its contact list and forces
- * (-5 when a requested readout's slot is unbound).  With BASECTL bound the relative
+ * (-5 when a requested readout's slot is unbound; the one exception: SMJ_READ_LIDAR with SMJ_SLOT_XPOSE unbound ray-casts from a pose
+ * workspace of the library's own, [nbody*12][num_envs] -- possible only when the slots' ld equals num_envs, otherwise -5 "bind
+ * SMJ_SLOT_XPOSE when the leading dimension differs from num_envs", nothing written).  With BASECTL bound the relative
  * base moves advance inside the launch (BaseController.update after every step) and CTRL's wheel entries are written back. */
 int smj_step(smj_ctx* ctx, int nsteps, unsigned read_flags, void* stream);
 

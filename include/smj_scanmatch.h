@@ -64,8 +64,9 @@ extern "C" {
  * evaluation; the inputs are unchanged; nothing outside the outputs is written (one workgroup per env).
  * Errors: -1 for a null lidar_dev / field_dev / pose_dev / angle_dev / pose_out_dev / best_dev, a pointer not aligned to 4 bytes
  * (field_dev excepted), nlidar > 1024, lidar_ld < num_envs, a frame that is no body id or a body id >= nbody, any limit above, an
- * output range that overlaps an input range or another output; -5 when SMJ_SLOT_XPOSE is not bound; -6 for a model without lidar
- * tables.  A refused call writes nothing. */
+ * output range that overlaps an input range or another output (the bound SMJ_SLOT_XPOSE is an input: its range runs from its first
+ * word to env num_envs-1 of its last row, as the scan's does -- columns beyond num_envs of the last row are free for an output); -5
+ * when SMJ_SLOT_XPOSE is not bound; -6 for a model without lidar tables.  A refused call writes nothing. */
 int smj_scan_to_pose(smj_ctx* ctx, const void* lidar_dev, long lidar_ld, int frame, float r_min, float r_max,
                      const void* field_dev, int nx, int ny, float x0, float y0, float cell,
                      const void* pose_dev, const void* angle_dev, const void* angle_bias_dev, int num_angles,

@@ -906,10 +906,11 @@ int smj_scan_to_pose(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame
   if (min_points < 1 || min_points > SMJ_MATCH_MAX_POINTS) return fail(c, -1, "min_points %d outside [1, %d]", min_points, (int)SMJ_MATCH_MAX_POINTS);
   // the workgroup of an env reads its inputs while others store
   const uintptr_t envs = (uintptr_t)c->num_envs, T = (uintptr_t)num_angles, cand = T * (uintptr_t)(2 * wy + 1) * (uintptr_t)(2 * wx + 1);
-  const uintptr_t ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
+  // (the slot's extent ends with the last env of its last row: the columns beyond num_envs are the caller's, an output may live there)
+  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
   TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
                          {pose_dev, envs * 12u, "pose"}, {angle_dev, T * 4u, "angle"}, {angle_bias_dev, T * 4u, "angle_bias"},
-                         {c->state.xpose, 12u * (uintptr_t)c->model.nbody_all * ld * 4u, "XPOSE slot's"}},
+                         {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
                      {{pose_out_dev, envs * 12u, "pose_out"}, {best_dev, envs * 16u, "best"}, {score_dev, envs * cand * 4u, "score"},
                       {cell_dev, envs * T * (uintptr_t)nlidar * 8u, "cell"}}));
   TRY(check_xpose(c));

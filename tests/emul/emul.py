@@ -77,10 +77,21 @@ def default_variant(blob: bytes) -> str:
     return rows[v][0]
 
 
+# what the padding of a store with ld > B holds (Emul(ld=...)): a NaN with a payload in the fp32 stores, -77 in the int32 ones, both as
+# int32 bit patterns -- the values of tests/capi_rig.py
+CANARY_BITS = {np.dtype(np.float32): 0x7FC0BEEF, np.dtype(np.int32): -77}
+
+
+def _canary_store(shape, dtype):
+    return np.full(shape, CANARY_BITS[np.dtype(dtype)], np.int32).view(dtype)
+
+
 class Emul:
-    def __init__(self, blob: bytes, dims: dict, num_envs: int = 1, debug: bool = True, variant: str | None = None):
+    def __init__(self, blob: bytes, dims: dict, num_envs: int = 1, debug: bool = True, variant: str | None = None, ld: int | None = None):
         """variant: a row of csrc/smj_variants.h ("standard", "mid", "big38", "big50", "big", "sat", "sat32") or a build tag ("tall",
-        "poison"); default: the one smj_create starts the model on, by the model's size and the blob's capacity hint."""
+        "poison"); default: the one smj_create starts the model on, by the model's size and the blob's capacity hint.
+        ld: the leading dimension the slots are bound with (default: num_envs, packed buffers).  With ld > num_envs every buffer is the
+        [:, :num_envs] view (zeroed) of a [rows, ld] array of self.store whose other columns hold CANARY_BITS."""
         if variant is None:
             variant = default_variant(blob)
             variant = "tall" if variant == "mid" else variant   # the one difference from smj_create: the emulator has no escalation of its own, so it runs `mid`'s hand-over target
@@ -93,24 +104,40 @@ class Emul:
             raise ValueError("emul_create failed")
         nq, nv, nu, nl = dims["nq"], dims["nv"], dims["nu"], dims["nlidar"]
         f = np.float32
-        self.buf = dict(qpos=np.zeros((nq, B), f), qvel=np.zeros((nv, B), f), ctrl=np.zeros((nu, B), f),
-                        warm=np.zeros((nv, B), f), nstep=np.zeros(B, np.int32), act_len=np.zeros((nu, B), f),
-                        act_vel=np.zeros((nu, B), f), base=np.zeros((3, B), f), gyro=np.zeros((3, B), f),
-                        accel=np.zeros((3, B), f), lidar=np.zeros((max(nl, 1), B), f), info=np.zeros((4, B), np.int32),
-                        bctl=np.zeros((8, B), f))
+        self.ld = B if ld is None else int(ld)
+        assert self.ld >= B
+        rows = dict(qpos=(nq, f), qvel=(nv, f), ctrl=(nu, f), warm=(nv, f), nstep=(None, np.int32), act_len=(nu, f), act_vel=(nu, f), base=(3, f),
+                    gyro=(3, f), accel=(3, f), lidar=(max(nl, 1), f), info=(4, np.int32), bctl=(8, f))
         if debug:
-            self.buf["debug"] = np.zeros((self.L.emul_debug_floats(), B), f)
-        for k, a in self.buf.items():
-            assert self.L.emul_bind(self.c, SLOTS[k], a.ctypes.data_as(ctypes.c_void_p), B) == 0
+            rows["debug"] = (self.L.emul_debug_floats(), f)
+        self.store, self.buf = {}, {}
+        for k, (n, dtype) in rows.items():
+            if self.ld == B:
+                self.store[k] = self.buf[k] = np.zeros(B if n is None else (n, B), dtype)
+            else:
+                self.store[k] = _canary_store(self.ld if n is None else (n, self.ld), dtype)
+                self.buf[k] = self.store[k][..., :B]
+                self.buf[k][...] = 0
+        self.bind(self.ld)
         # PGS: the emulator starts the sweeps the way MuJoCo does unless a test asks for the kernels' default (a second start from the
         # previous step's forces, option pgs_dual_warmstart = 1) -- most PGS tests compare iterate for iterate with the unmodified oracle
         self.set_option("pgs_dual_warmstart", 0)
 
+    def bind(self, ld: int):
+        """Bind every buffer with leading dimension `ld` (tests of the stride itself pass another one than the stores have)."""
+        for k, a in self.store.items():
+            assert self.L.emul_bind(self.c, SLOTS[k], a.ctypes.data_as(ctypes.c_void_p), ld) == 0
+
     def bind_contacts(self, cap: int):
         """The contact-readout slot (SMJ_SLOT_CONTACTS): self.rec, env-major [B, cap, CONTACT_WORDS], written by a step with
-        lib.READ_CONTACTS; never-written words stay NaN."""
+        lib.READ_CONTACTS; never-written words stay NaN (the one of CANARY_BITS).  With ld > B it is the [:B] view of self.rec_store,
+        [ld, cap, CONTACT_WORDS]."""
         assert self.L.emul_contact_words() == CONTACT_WORDS
-        self.rec = np.full((self.B, cap, CONTACT_WORDS), np.nan, np.float32)
+        if self.ld == self.B:
+            self.rec_store = self.rec = _canary_store((self.B, cap, CONTACT_WORDS), np.float32)
+        else:
+            self.rec_store = _canary_store((self.ld, cap, CONTACT_WORDS), np.float32)
+            self.rec = self.rec_store[:self.B]
         assert self.L.emul_bind_contacts(self.c, self.rec.ctypes.data_as(ctypes.c_void_p), cap) == 0
 
     def set_option(self, name, v):

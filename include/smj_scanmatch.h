@@ -76,4 +76,5 @@ int smj_scan_to_pose(smj_ctx* ctx, const void* lidar_dev, long lidar_ld, int fra
 #ifdef __cplusplus
 }
 #endif
+#include "smj_mapping.h"
 #endif

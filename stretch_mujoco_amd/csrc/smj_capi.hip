@@ -30,6 +30,7 @@
 #include "smj_front.h"
 #include "smj_drive.h"
 #include "smj_match.h"
+#include "smj_map.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -919,6 +920,42 @@ int smj_scan_to_pose(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame
                    c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
                    (const float*)pose_dev, (const float*)angle_dev, (const int*)angle_bias_dev, num_angles, wx, wy, shift_weight, min_points,
                    (float*)pose_out_dev, (int*)best_dev, (int*)score_dev, (int*)cell_dev, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static_assert((int)SMJ_MAP_MAX_RAYS == (int)SMJ_MATCH_MAX_POINTS, "smj_map.h integrates the scans smj_match.h matches, at the poses it finds");
+
+int smj_scan_to_map(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame, float r_min, float r_max, const void* pose_dev, const void* gate_dev, long gate_ld,
+                    float x0, float y0, float cell, int nx, int ny, int no_return_clears, int accumulate, void* hit_dev, void* miss_dev, void* info_dev,
+                    void* cell_dev, void* stream) {
+  if (!c) return -1;
+  FrameKind fk;
+  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to map");
+  if (!lidar_dev || !pose_dev || !hit_dev || !info_dev) return fail(c, -1, "null scan / pose / hit / info buffer");
+  TRY(check_aligned(c, {lidar_dev, pose_dev, gate_dev, hit_dev, miss_dev, info_dev, cell_dev}, "scan / pose / gate / hit / miss / info / cell buffer"));
+  const int nlidar = c->render.nlidar;
+  if (nlidar > SMJ_MAP_MAX_RAYS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MAP_MAX_RAYS);
+  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  if (gate_ld < 1) return fail(c, -1, "gate_ld %ld below 1", gate_ld);
+  TRY(check_cell_grid(c, nx, ny, SMJ_OCC_MAX_CELLS, SMJ_OCC_MAX_CELLS));   // the grids of smj_lidar_to_occupancy: no bound on a side but the cell count
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
+  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d: a ray would cross more cells than the line arithmetic takes", (int)SMJ_OCC_MAX_STEPS);
+  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
+  TRY(check_frame(c, frame, false, &fk));
+  // the workgroups of an env read its inputs while others store
+  const uintptr_t envs = (uintptr_t)c->num_envs, cells = envs * (uintptr_t)nx * (uintptr_t)ny;
+  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
+  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {pose_dev, envs * 12u, "pose"},
+                         {gate_dev, ((envs - 1) * (uintptr_t)gate_ld + 1) * 4u, "gate"}, {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
+                     {{hit_dev, cells * 4u, "hit"}, {miss_dev, cells * 4u, "miss"}, {info_dev, envs * 16u, "info"}, {cell_dev, envs * (uintptr_t)nlidar * 16u, "cell"}}));
+  TRY(check_xpose(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_map(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
+                 c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const float*)pose_dev, (const int*)gate_dev, gate_ld, x0, y0, cell,
+                 nx, ny, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (int*)info_dev, (int*)cell_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -443,6 +443,36 @@ class StatusStretchScanMatch:
 
 
 @dataclass
+class StatusStretchMapUpdate:
+    """New, without a reference counterpart: what pull_map_update() (smj_scan_to_map) did with the lidar scan of the last step -- the
+    map it was added to, as a StatusStretchOccupancyGrid that pull_distance_field(), pull_scan_match(), pull_frontiers() and
+    pull_navigation_field() take as it is, and per env whether and how much was integrated.  Device tensors, simulator-owned, not
+    synchronised to the host."""
+    time: Any
+    grid: Any           # StatusStretchOccupancyGrid: the map after the update; its tensors are the ones handed in, or the simulator's
+    info: Any           # [B, 4] int32: the status, the returns kept, the clearing rays kept, the rays a guard dropped (0, 0, 0 unless the status is 0)
+    cells: Any          # [B, nlidar, 4] int32 or None: (ax, ay, bx, by) of every kept ray, NO_CELL four times where it has none
+
+    OK, GATED, OFF = 0, 1, 2      # SMJ_MAP_*
+    NO_CELL = -(1 << 30)          # SMJ_MAP_NO_CELL
+
+    @property
+    def status(self):
+        """int32 [B]: 0 integrated, 1 held back by the gate, 2 the pose is not finite."""
+        return self.info[:, 0]
+
+    def integrated(self):
+        return self.info[:, 0] == self.OK
+
+    def gated(self):
+        return self.info[:, 0] == self.GATED
+
+    def returns(self):
+        """int32 [B]: the returns that went into the map, 0 for an env that was not integrated."""
+        return self.info[:, 1]
+
+
+@dataclass
 class StatusStretchNavigationField:
     """New, without a reference counterpart: the exact cost-to-goal field of pull_navigation_field() (smj_costmap_to_navigation) over
     a grid laid out as StatusStretchOccupancyGrid's.  `potential` and `next` are exact integers; the helpers turn them into metres,

@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchScanMatch, StatusStretchSensors, cells_of_points
+from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchMapUpdate, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchScanMatch, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -149,6 +149,7 @@ class StretchBatchSimulator:
         self._drive = {}            # (K, P, ny, nx) -> the simulator-owned cmd, best, score, cells, twist and pose of pull_base_command
         self._drive_default = None  # arc_candidates() on the device, made by the first pull_base_command without a table
         self._match = {}            # (T, wx, wy, ny, nx) -> the simulator-owned pose, best, score, cells and prior of pull_scan_match
+        self._maps = {}             # (ny, nx) -> the simulator-owned hit, miss, info and cells of pull_map_update
         self._match_default = None  # scan_angles() on the device, made by the first pull_scan_match without a table
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
@@ -1000,6 +1001,88 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_scan_to_pose")
         return StatusStretchScanMatch(time=self._time(), pose=bufs["pose"], best=bufs["best"], score=score_t, cells=cells_t, angles=ang,
                                       window=(wx, wy), origin=x0y0, cell=cell, frame=frame, bias=bias, shift_weight=shift_weight)
+
+    @_require_connection
+    def pull_map_update(self, pose, grid=None, gate=None, *, origin=(-3.2, -3.2), cell: float = 0.05, shape=(128, 128), range_limits=(0.2, 5.0),
+                        no_return_clears: bool = True, accumulate: bool = True, cells: bool = False) -> StatusStretchMapUpdate:
+        """The lidar scan of the last step ray-traced into a map at a pose that is handed in, in one HIP pass (smj_scan_to_map,
+        include/smj_mapping.h): what pull_occupancy_grid(frame="world", accumulate=True) does with the simulator's own pose, done with
+        the pose an estimator believes in.  With pull_scan_match() before it and pull_distance_field() after it this closes the loop
+        -- match, integrate, distance field, match again -- per env on the device, nothing read back.  Integer sums: two calls give
+        identical tensors.  New, without a reference counterpart: it stands where a user of the real robot runs slam_toolbox.
+
+        pose: float [3, B] on the device (x, y, theta in the map's frame); match.pose goes in as it is.
+        grid: a StatusStretchOccupancyGrid to add into -- its tensors, origin, cell and frame are taken over (origin, cell and shape
+        of this call are not looked at); the first scan may have been mapped by pull_occupancy_grid(frame="world"), say.  A "base"
+        grid moves with the robot and is no map (ValueError).  None: simulator-owned buffers of `shape` at origin and cell, zeroed
+        when first used, in the frame "world".
+        gate: None; an int32 [B] tensor on the device -- env e is integrated iff gate[e] == 0; or a StatusStretchScanMatch, whose
+        status column is read where it lies (only envs whose match is ok are integrated).  An env whose pose is not finite is never
+        integrated.  An env that is not integrated keeps its map (accumulate=True) or gets zeros (accumulate=False).
+        range_limits, no_return_clears: as in pull_occupancy_grid.  cells: also return (ax, ay, bx, by) of every ray.
+        update.grid goes into pull_distance_field(), pull_scan_match(), pull_frontiers() and pull_navigation_field() as it is.
+        Needs StretchSensors.base_lidar in sensors_to_use.
+        The tensors are simulator-owned and overwritten (the map: added to) by the next call with the same shape."""
+        B, dev = self.num_envs, self.device
+        if not self._read_flags & _lib.READ_LIDAR:
+            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+        if self.nlidar > 1024:
+            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_map takes 1024")
+        if not isinstance(pose, torch.Tensor) or not pose.is_floating_point() or tuple(pose.shape) != (3, B) or pose.device != dev:
+            raise ValueError(f"pose: a float tensor [3, num_envs = {B}] on {dev}")
+        if grid is None:
+            ny, nx, x0, y0, cell, r_min, r_max = self._grid_args(shape, origin, cell, range_limits, "range_limits = (r_min, r_max)")
+            frame, hit, miss = "world", None, None
+        else:
+            if not isinstance(grid, StatusStretchOccupancyGrid):
+                raise ValueError("grid: None or a StatusStretchOccupancyGrid")
+            (x0, y0), cell = self._origin_cell(grid, None, None)
+            frame, hit, miss = grid.frame, grid.hit, grid.miss
+            for t in (hit, miss):
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != B or t.dtype != torch.int32 or not t.is_contiguous()
+                                      or t.device != dev or (hit is not None and t.shape != hit.shape)):
+                    raise ValueError(f"grid: contiguous int32 [num_envs = {B}, ny, nx] on {dev}")
+            if hit is None:
+                raise ValueError("grid: a map has a hit layer")
+            ny, nx, x0, y0, cell, r_min, r_max = self._grid_args(hit.shape[1:], (x0, y0), cell, range_limits, "range_limits = (r_min, r_max)")
+        if frame not in ("world", "grid"):
+            raise ValueError('the grid\'s frame must be "world" or "grid": a "base" grid moves with the robot and is no map')
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
+            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
+        if np.float32(r_max) / np.float32(cell) > 8192:
+            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        gate_t, gate_at, gate_ld = None, None, 1
+        if isinstance(gate, StatusStretchScanMatch):
+            gate_t = gate.best
+            if not isinstance(gate_t, torch.Tensor) or gate_t.dtype != torch.int32 or tuple(gate_t.shape) != (B, 4) or not gate_t.is_contiguous() or gate_t.device != dev:
+                raise ValueError(f"gate: the match's best must be a contiguous int32 [num_envs = {B}, 4] on {dev}")
+            gate_at, gate_ld = gate_t.data_ptr() + 12, 4      # the status column, where it lies
+        elif gate is not None:
+            if not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or tuple(gate.shape) != (B,) or gate.device != dev or (B > 1 and gate.stride(0) < 1):
+                raise ValueError(f"gate: None, an int32 tensor [num_envs = {B}] on {dev}, or a StatusStretchScanMatch")
+            gate_t, gate_at, gate_ld = gate, gate.data_ptr(), max(int(gate.stride(0)), 1)
+        body, offset = self._base_frame()
+        if offset is not None:
+            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's rays cannot be formed in "
+                             "the robot's frame")
+        # every ValueError has been raised: from here on the device works
+        new = lambda *shape: torch.empty(B, *shape, dtype=torch.int32, device=dev)
+        bufs = self._cached(self._maps, (ny, nx), lambda: dict(hit=None, miss=None, info=new(4), cells=None))
+        if grid is None:
+            if bufs["hit"] is None:
+                bufs["hit"], bufs["miss"] = torch.zeros(B, ny, nx, dtype=torch.int32, device=dev), torch.zeros(B, ny, nx, dtype=torch.int32, device=dev)
+            hit, miss = bufs["hit"], bufs["miss"]
+        if cells and bufs["cells"] is None:
+            bufs["cells"] = new(self.nlidar, 4)
+        cells_t = bufs["cells"] if cells else None
+        pose_t = pose if pose.dtype == torch.float32 and pose.is_contiguous() else pose.to(torch.float32).contiguous()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self._L.smj_scan_to_map(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(pose_t), ctypes.c_void_p(gate_at) if gate_at is not None else None, gate_ld,
+                                     x0, y0, cell, nx, ny, int(bool(no_return_clears)), int(bool(accumulate)), vp(hit), vp(miss), vp(bufs["info"]), vp(cells_t),
+                                     self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_scan_to_map")
+        out = StatusStretchOccupancyGrid(time=self._time(), hit=hit, miss=miss, origin=(x0, y0), cell=cell, frame=frame)
+        return StatusStretchMapUpdate(time=out.time, grid=out, info=bufs["info"], cells=cells_t)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

@@ -79,4 +79,5 @@ int smj_scan_to_map(smj_ctx* ctx, const void* lidar_dev, long lidar_ld, int fram
 #ifdef __cplusplus
 }
 #endif
+#include "smj_localize.h"
 #endif

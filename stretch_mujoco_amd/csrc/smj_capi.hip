@@ -31,6 +31,7 @@
 #include "smj_drive.h"
 #include "smj_match.h"
 #include "smj_map.h"
+#include "smj_mcl.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -56,6 +57,7 @@ struct smj_ctx {
   int* cost = nullptr;
   int* order = nullptr;
   int lidar_cull = 1;      // lidar: drop, per env, the geoms that cannot reach the scan plane (smj_render.h lidar_plane_*)
+  int mcl_stage_field = 1; // smj_scan_to_particles: the env's field is copied into LDS (0: gathered through L2; the weights must not change)
   bool prof_warned = false;    // the one-time warning of smj_step: profiling slot bound, the PGS kernel launched has no counters
   const SmjBuildDesc* last_primary = nullptr;   // the primary build of the last smj_step (smj_last_build)
   int* progress = nullptr;    // [B] progress, [B] done_steps, [SMJ_SCHED_WORDS] sched (DevState)
@@ -960,11 +962,58 @@ int smj_scan_to_map(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame,
   return 0;
 }
 
+static_assert((int)SMJ_MCL_MAX_POINTS == (int)SMJ_MATCH_MAX_POINTS, "smj_mcl.h weighs particles by the scans and fields smj_match.h matches");
+
+int smj_scan_to_particles(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame, float r_min, float r_max, const void* field_dev, int nx, int ny,
+                          float x0, float y0, float cell, const void* particle_dev, int num_particles, const void* noise_dev, const void* draw_dev, int span,
+                          int min_points, int resample, void* particle_out_dev, void* weight_dev, void* ancestor_dev, void* stat_dev, void* pose_out_dev,
+                          void* stream) {
+  if (!c) return -1;
+  FrameKind fk;
+  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to weigh particles by");
+  if (!lidar_dev || !field_dev || !particle_dev || !particle_out_dev || !weight_dev || !stat_dev)
+    return fail(c, -1, "null scan / field / particle / particle_out / weight / stat buffer");
+  if (resample != 0 && resample != 1) return fail(c, -1, "resample %d is neither 0 nor 1", resample);
+  if (resample && !draw_dev) return fail(c, -1, "null draw buffer with resample = 1");
+  TRY(check_aligned(c, {lidar_dev, particle_dev, noise_dev, draw_dev, particle_out_dev, weight_dev, ancestor_dev, stat_dev, pose_out_dev},
+                    "scan / particle / noise / draw / particle_out / weight / ancestor / stat / pose_out buffer"));
+  const int nlidar = c->render.nlidar;
+  if (nlidar > SMJ_MCL_MAX_POINTS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MCL_MAX_POINTS);
+  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_cell_grid(c, nx, ny, SMJ_MATCH_MAX_SIDE, SMJ_MATCH_MAX_CELLS));
+  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
+  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
+  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d, the bound of smj_lidar_to_occupancy", (int)SMJ_OCC_MAX_STEPS);
+  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
+  TRY(check_frame(c, frame, false, &fk));
+  if (num_particles < 1 || num_particles > SMJ_MCL_MAX_PARTICLES) return fail(c, -1, "num_particles %d outside [1, %d]", num_particles, (int)SMJ_MCL_MAX_PARTICLES);
+  if (span < 1 || span > SMJ_MCL_MAX_SPAN) return fail(c, -1, "span %d outside [1, %d]", span, (int)SMJ_MCL_MAX_SPAN);
+  if (min_points < 1 || min_points > SMJ_MCL_MAX_POINTS) return fail(c, -1, "min_points %d outside [1, %d]", min_points, (int)SMJ_MCL_MAX_POINTS);
+  // the workgroup of an env reads its inputs while others store
+  const uintptr_t envs = (uintptr_t)c->num_envs, words = envs * (uintptr_t)num_particles;
+  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
+  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
+                         {particle_dev, words * 12u, "particle"}, {noise_dev, words * 12u, "noise"}, {draw_dev, envs * 4u, "draw"},
+                         {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
+                     {{particle_out_dev, words * 12u, "particle_out"}, {weight_dev, words * 4u, "weight"}, {ancestor_dev, words * 4u, "ancestor"},
+                      {stat_dev, envs * 4u * (uintptr_t)SMJ_MCL_STAT_WORDS, "stat"}, {pose_out_dev, envs * 12u, "pose_out"}}));
+  TRY(check_xpose(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  smj_launch_mcl(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
+                 c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
+                 (const float*)particle_dev, num_particles, (const float*)noise_dev, (const unsigned*)draw_dev, span, min_points, resample,
+                 (float*)particle_out_dev, (int*)weight_dev, (int*)ancestor_dev, (int*)stat_dev, (float*)pose_out_dev, c->mcl_stage_field, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
 int smj_set_option(smj_ctx* c, const char* name, double v) {
   if (!c || !name) return -1;
   DevModel& m = c->model;
   if (!strcmp(name, "lidar_cull")) c->lidar_cull = (int)v;                  // 1 (default): per env, only the geoms whose bounding sphere reaches the rangefinders' scan plane are staged
-  else if (!strcmp(name, "depth_raster")) c->render.raster = (int)v;            // 0: ray cast the meshes through their BVHs (the round-2 path)
+  else if (!strcmp(name, "mcl_stage_field")) c->mcl_stage_field = (int)v != 0;   // 1 (default): smj_scan_to_particles keeps the env's field in LDS; 0: it stays in global memory (profiles/localize_cost.txt has both)
+  else if (!strcmp(name, "depth_raster")) c->render.raster = (int)v;           // 0: ray cast the meshes through their BVHs (the round-2 path)
   else if (!strcmp(name, "depth_raster_splits")) c->render.raster_splits = (int)(v < 1 ? 1 : v > 256 ? 256 : v);
   else if (!strcmp(name, "primary_rows")) m.row_limit = (int)v;   // the escalation variant keeps its full capacity (model_esc is not touched)
   else if (smj_set_step_option(c->opt, name, v)) {}   // the scheduling options, by the list of smj_step_plan.h

@@ -473,6 +473,108 @@ class StatusStretchMapUpdate:
 
 
 @dataclass
+class StatusStretchParticles:
+    """New, without a reference counterpart: one measurement update of a particle filter, pull_particle_update()
+    (smj_scan_to_particles) -- per env P pose hypotheses weighted by the lidar scan of the last step against a likelihood field,
+    and resampled.  `particles` goes into the next call (after predict(), when the robot has moved); `pose`, the best particle, is
+    what pull_scan_match(prior=...), pull_map_update() and pull_base_command(pose=...) take; `stat[:, 3]` gates pull_map_update()
+    where it lies.  Everything after the weights is integers, so two calls give identical tensors.  Device tensors,
+    simulator-owned, not synchronised to the host."""
+    time: Any
+    particles: Any      # [3, B, P] fp32: rows x, y, theta in the field's frame AFTER the update: resampled (plus noise) with status 0 and resample, the input bit for bit otherwise
+    weights: Any        # [B, P] int32: S of every INPUT particle, the sum of the field under the scan's returns laid out from it, whatever the status
+    ancestors: Any      # [B, P] int32 or None: the input particle slot k was drawn from; k itself where nothing was resampled
+    stat: Any           # [B, 8] int32: the best particle (-1 unless status 0), its S, the counted returns n, the status, total, the effective sample size, cut, the distinct ancestors
+    pose: Any           # [3, B] fp32: the best INPUT particle with status 0, NaN otherwise
+    prior: Any          # [3, B, P] fp32: the particles that were weighed (the input of the call, as the kernel read it)
+    origin: Any         # (x0, y0): the corner of cell (0, 0)
+    cell: float
+    frame: str          # "world" or "grid"
+
+    OK, FEW, LOST = 0, 1, 2      # SMJ_MCL_*
+
+    @property
+    def status(self):
+        """int32 [B]: 0 ok, 1 fewer returns than min_points, 2 no particle puts a return on a rewarded cell."""
+        return self.stat[:, 3]
+
+    def ok(self):
+        return self.stat[:, 3] == self.OK
+
+    def few(self):
+        return self.stat[:, 3] == self.FEW
+
+    def lost(self):
+        return self.stat[:, 3] == self.LOST
+
+    def best(self):
+        """int32 [B]: the input particle with the largest S, the smallest index among equal S; -1 unless ok()."""
+        return self.stat[:, 0]
+
+    def ess(self):
+        """int32 [B]: the effective sample size floor(total^2 / sum of w^2) of the input particles, between 1 and P; 0 unless ok()."""
+        return self.stat[:, 5]
+
+    def total(self):
+        """int32 [B]: the sum of w; 0 unless ok()."""
+        return self.stat[:, 4]
+
+    def w(self):
+        """int32 [B, P]: w_j = max(S_j - cut, 0), what the resampling drew by, recomputed from `weights` and the cut in `stat`."""
+        return (self.weights - self.stat[:, 6:7]).clamp(min=0)
+
+    def _moments(self):
+        import torch
+
+        w = self.w().to(torch.float64)                                     # [B, P]
+        live = w > 0                                                       # a particle of weight 0 may be anything, NaN included
+        p = torch.where(live.unsqueeze(0), self.prior.to(torch.float64), torch.zeros((), dtype=torch.float64, device=w.device))
+        return w, p, w.sum(1)
+
+    def mean(self):
+        """fp32 [3, B]: the mean pose of the INPUT particles weighted by w (summed in fp64), theta as the direction of the mean unit
+        vector; NaN for an env whose weights sum to 0.  With few particles left far from the best one this is the smoother estimate;
+        `pose` is the one that is exact."""
+        import torch
+
+        w, p, tot = self._moments()
+        x, y = (w * p[0]).sum(1) / tot, (w * p[1]).sum(1) / tot
+        th = torch.atan2((w * torch.sin(p[2])).sum(1) / tot, (w * torch.cos(p[2])).sum(1) / tot)
+        return torch.stack((x, y, th), 0).to(torch.float32)
+
+    def spread(self):
+        """fp32 [3, B]: the weighted standard deviations of x and y [m] about mean(), and the circular standard deviation of theta
+        [rad], sqrt(-2 ln R) with R the length of the mean unit vector; NaN for an env whose weights sum to 0."""
+        import torch
+
+        w, p, tot = self._moments()
+        mx, my = (w * p[0]).sum(1) / tot, (w * p[1]).sum(1) / tot
+        sx = torch.sqrt((w * (p[0] - mx.unsqueeze(1)) ** 2).sum(1) / tot)
+        sy = torch.sqrt((w * (p[1] - my.unsqueeze(1)) ** 2).sum(1) / tot)
+        R = torch.hypot((w * torch.sin(p[2])).sum(1) / tot, (w * torch.cos(p[2])).sum(1) / tot).clamp(max=1.0)
+        return torch.stack((sx, sy, torch.sqrt(-2.0 * torch.log(R))), 0).to(torch.float32)
+
+    def predict(self, delta, noise=None):
+        """fp32 [3, B, P], a new tensor: every particle of `particles` moved by the odometry increment delta = (dx, dy, dtheta), given
+        in the robot's frame (x forward, y left) as three numbers or a tensor [3] or [3, B], plus noise [3, B, P] (None: none;
+        utils.particle_noise).  Elementwise torch: the motion update between two pull_particle_update() calls."""
+        import torch
+
+        part = self.particles
+        d = torch.as_tensor(delta, dtype=torch.float32, device=part.device)
+        if d.dim() not in (1, 2) or d.shape[0] != 3 or (d.dim() == 2 and d.shape[1] != part.shape[1]):
+            raise ValueError(f"delta: (dx, dy, dtheta) as [3] or [3, num_envs = {part.shape[1]}]")
+        d = d.reshape(3, -1, 1)
+        c, s = torch.cos(part[2]), torch.sin(part[2])
+        out = torch.stack((part[0] + c * d[0] - s * d[1], part[1] + s * d[0] + c * d[1], part[2] + d[2]), 0)
+        if noise is not None:
+            if tuple(noise.shape) != tuple(part.shape):
+                raise ValueError(f"noise: None or a tensor {tuple(part.shape)}")
+            out = out + noise.to(out.dtype)
+        return out
+
+
+@dataclass
 class StatusStretchNavigationField:
     """New, without a reference counterpart: the exact cost-to-goal field of pull_navigation_field() (smj_costmap_to_navigation) over
     a grid laid out as StatusStretchOccupancyGrid's.  `potential` and `next` are exact integers; the helpers turn them into metres,

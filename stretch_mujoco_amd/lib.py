@@ -30,6 +30,7 @@ FRONTIER_EXPORTS = ("smj_occupancy_to_frontiers",)   # include/smj_frontier.h (s
 DRIVE_EXPORTS = ("smj_navigation_to_velocity",)   # include/smj_drive.h (smj_frontier.h includes it, so smj.h does)
 SCANMATCH_EXPORTS = ("smj_scan_to_pose",)   # include/smj_scanmatch.h (smj_drive.h includes it, so smj.h does)
 MAPPING_EXPORTS = ("smj_scan_to_map",)   # include/smj_mapping.h (smj_scanmatch.h includes it, so smj.h does)
+LOCALIZE_EXPORTS = ("smj_scan_to_particles",)   # include/smj_localize.h (smj_mapping.h includes it, so smj.h does)
 BUILD_EXPORTS =("smj_last_build",)   # include/smj_build.h (a header of its own: smj.h does not include it)
 DIST_NONE = 1 << 30   # SMJ_DIST_NONE: dist2 of a cell with no obstacle in reach
 NAV_NONE = 1 << 30   # SMJ_NAV_NONE: potential of a cell from which no goal can be reached
@@ -100,6 +101,7 @@ def load() -> ctypes.CDLL:
     L.smj_navigation_to_velocity.argtypes = [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp]
     L.smj_scan_to_pose.argtypes = [vp, vp, cl, ci, cf, cf, vp, ci, ci, cf, cf, cf, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.smj_scan_to_map.argtypes = [vp, vp, cl, ci, cf, cf, vp, vp, cl, cf, cf, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.smj_scan_to_particles.argtypes = [vp, vp, cl, ci, cf, cf, vp, ci, ci, cf, cf, cf, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.smj_set_option.argtypes =[vp, ctypes.c_char_p, ctypes.c_double]
     L.smj_base_controller_tick.argtypes = [vp, vp]
     L.smj_comm_init.argtypes = [vp, ci, ci, ctypes.c_char_p, ctypes.c_double]

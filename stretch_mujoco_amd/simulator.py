@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _lib
 from . import model_blob
-from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchMapUpdate, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchScanMatch, StatusStretchSensors, cells_of_points
+from .datamodels import StatusStretchBaseCommand, StatusStretchCameras,StatusStretchContacts, StatusStretchDistanceField, StatusStretchFrontiers, StatusStretchHeightMap, StatusStretchJoints, StatusStretchMapUpdate, StatusStretchNavigationField, StatusStretchOccupancyGrid, StatusStretchParticles, StatusStretchScanMatch, StatusStretchSensors, cells_of_points
 from .enums import Actuators, StretchCameras, StretchSensors
 from .glue import Glue
 
@@ -151,6 +151,8 @@ class StretchBatchSimulator:
         self._match = {}            # (T, wx, wy, ny, nx) -> the simulator-owned pose, best, score, cells and prior of pull_scan_match
         self._maps = {}             # (ny, nx) -> the simulator-owned hit, miss, info and cells of pull_map_update
         self._match_default = None  # scan_angles() on the device, made by the first pull_scan_match without a table
+        self._particles = {}        # (P, ny, nx) -> the simulator-owned tensors of pull_particle_update: two particle sets that take turns, weights, ancestors, stat, pose, draw
+        self._draw_generator = None # the torch.Generator on the device that pull_particle_update(draw=None) draws its random words from
         self._dist = {}             # (ny, nx) -> the simulator-owned [dist2, nearest or None] of pull_distance_field
         self._points = {}           # (camera, stride) -> the simulator-owned point cloud of pull_point_cloud
         # body poses of the last step: input of the depth renderer and of get_link_pose (240 floats per env, always on)
@@ -884,6 +886,43 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_navigation_to_velocity")
         return StatusStretchBaseCommand(time=self._time(), cmd=bufs["cmd"], best=bufs["best"], score=score_t, cells=cells_t, frame=nav.frame)
 
+    def _match_field(self, field, sigma, origin, cell):
+        """The field argument of pull_scan_match() and pull_particle_update(), checked: (field, grid, sigma, (x0, y0), cell, frame,
+        ny, nx).  `grid` is the StatusStretchOccupancyGrid a field is still to be made of (then field is None); nothing is launched."""
+        B, dev = self.num_envs, self.device
+        grid = None
+        if isinstance(field, (StatusStretchDistanceField, StatusStretchOccupancyGrid)):
+            src = field.dist2 if isinstance(field, StatusStretchDistanceField) else field.hit
+            if not isinstance(src, torch.Tensor) or src.dim() != 3 or src.shape[0] != B or src.dtype != torch.int32 or src.device != dev:
+                raise ValueError(f"field: int32 tensors [num_envs = {B}, ny, nx] on {dev}")
+            x0y0, cell = self._origin_cell(field, origin, cell)
+            frame, (ny, nx) = field.frame, (int(v) for v in src.shape[1:])
+            sigma = float(sigma)
+            if not (0 < sigma < float("inf")):
+                raise ValueError("sigma: metres, finite and > 0")
+            if isinstance(field, StatusStretchOccupancyGrid):
+                grid, field = field, None
+        else:
+            if not isinstance(field, torch.Tensor) or field.dtype != torch.uint8 or field.dim() != 3 or field.shape[0] != B:
+                raise ValueError(f"field: a StatusStretchDistanceField, a StatusStretchOccupancyGrid, or a uint8 tensor [num_envs = {B}, ny, nx]")
+            if origin is None or cell is None:
+                raise ValueError("a bare field needs origin = (x0, y0) and cell")
+            x0y0, cell = self._origin_cell(None, origin, cell)
+            frame, (ny, nx) = "grid", (int(v) for v in field.shape[1:])
+        if frame not in ("world", "grid"):
+            raise ValueError('the field\'s frame must be "world" or "grid": a "base" grid moves with the robot and is no map')
+        self._check_cell_count("field", ny, nx)
+        return field, grid, sigma, x0y0, cell, frame, ny, nx
+
+    def _match_field_tensor(self, field, grid, sigma):
+        """The uint8 field on the device, after every ValueError has been raised: the distance field of `grid` and its likelihood
+        where the caller handed in a map."""
+        if grid is not None:
+            field = self.pull_distance_field(grid)
+        if isinstance(field, StatusStretchDistanceField):
+            field = field.likelihood(sigma)
+        return field.to(device=self.device).contiguous()
+
     @_require_connection
     def pull_scan_match(self, field, prior=None, *, sigma: float = 0.10, window=(0.5, 0.5), angles=None, range_limits=(0.2, 5.0),
                         min_points: int = 30, shift_weight: int = 0, scores: bool = False, cells: bool = False, origin=None,
@@ -915,28 +954,7 @@ class StretchBatchSimulator:
             raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
         if self.nlidar > 1024:
             raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_pose takes 1024")
-        grid = None
-        if isinstance(field, (StatusStretchDistanceField, StatusStretchOccupancyGrid)):
-            src = field.dist2 if isinstance(field, StatusStretchDistanceField) else field.hit
-            if not isinstance(src, torch.Tensor) or src.dim() != 3 or src.shape[0] != B or src.dtype != torch.int32 or src.device != dev:
-                raise ValueError(f"field: int32 tensors [num_envs = {B}, ny, nx] on {dev}")
-            x0y0, cell = self._origin_cell(field, origin, cell)
-            frame, (ny, nx) = field.frame, (int(v) for v in src.shape[1:])
-            sigma = float(sigma)
-            if not (0 < sigma < float("inf")):
-                raise ValueError("sigma: metres, finite and > 0")
-            if isinstance(field, StatusStretchOccupancyGrid):
-                grid, field = field, None
-        else:
-            if not isinstance(field, torch.Tensor) or field.dtype != torch.uint8 or field.dim() != 3 or field.shape[0] != B:
-                raise ValueError(f"field: a StatusStretchDistanceField, a StatusStretchOccupancyGrid, or a uint8 tensor [num_envs = {B}, ny, nx]")
-            if origin is None or cell is None:
-                raise ValueError("a bare field needs origin = (x0, y0) and cell")
-            x0y0, cell = self._origin_cell(None, origin, cell)
-            frame, (ny, nx) = "grid", (int(v) for v in field.shape[1:])
-        if frame not in ("world", "grid"):
-            raise ValueError('the field\'s frame must be "world" or "grid": a "base" grid moves with the robot and is no map')
-        self._check_cell_count("field", ny, nx)
+        field, grid, sigma, x0y0, cell, frame, ny, nx = self._match_field(field, sigma, origin, cell)
         try:
             r_min, r_max = (float(v) for v in range_limits)
             wx, wy = (int(round(float(v) / cell)) for v in window)
@@ -972,11 +990,7 @@ class StretchBatchSimulator:
             raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's points cannot be formed in "
                              "the robot's frame")
         # every ValueError has been raised: from here on the device works
-        if grid is not None:
-            field = self.pull_distance_field(grid)
-        if isinstance(field, StatusStretchDistanceField):
-            field = field.likelihood(sigma)
-        field = field.to(device=dev).contiguous()
+        field = self._match_field_tensor(field, grid, sigma)
         new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
         bufs = self._cached(self._match, (T, wx, wy, ny, nx), lambda: dict(pose=new(torch.float32, 3, B), best=new(torch.int32, B, 4), score=None,
                                                                             cells=None, prior=None))
@@ -1083,6 +1097,94 @@ class StretchBatchSimulator:
         _lib.check(self._L, self._ctx, rc, "smj_scan_to_map")
         out = StatusStretchOccupancyGrid(time=self._time(), hit=hit, miss=miss, origin=(x0, y0), cell=cell, frame=frame)
         return StatusStretchMapUpdate(time=out.time, grid=out, info=bufs["info"], cells=cells_t)
+
+    @_require_connection
+    def pull_particle_update(self, field, particles, noise=None, draw=None, span: int = 4096, min_points: int = 30, resample: bool = True,
+                             range_limits=(0.2, 5.0), ancestors: bool = False, origin=None, cell=None, *, sigma: float = 0.10) -> StatusStretchParticles:
+        """One measurement update of a particle filter for every env, in one HIP pass (smj_scan_to_particles, include/smj_localize.h):
+        Monte Carlo localisation.  Per env P pose hypotheses -- anywhere on the map, each with its own heading, no lattice -- are
+        weighted by the sum S of a likelihood field under the returns of the lidar scan of the last step, laid out from the particle,
+        and resampled (systematic resampling, one random word per env) by w = max(S - cut, 0), cut = max(S_max - span, 0).  Where
+        pull_scan_match() searches +-0.5 m and +-5 degrees round one prior, this finds a robot whose pose is unknown by metres; its
+        best particle is then the prior the matcher refines to the cell.  Everything after the weights is integers: two calls give
+        identical tensors.  Nothing is read back to the host.  New, without a reference counterpart: it stands where a user of the
+        real robot runs AMCL.
+
+        field: as pull_scan_match() takes it -- a StatusStretchDistanceField, whose likelihood(sigma) is used and whose frame, origin
+        and cell are taken over; a StatusStretchOccupancyGrid, which goes through pull_distance_field() first; or a uint8 tensor
+        [B, ny, nx] with origin= and cell=.
+        particles: float [3, B, P] on the device, rows x, y, theta in the field's frame, 1 <= P <= 4096 (utils.spread_particles for
+        a first set; update.particles, or update.predict(odometry) when the robot has moved, for the next call).  A particle that is
+        not finite weighs nothing and dies out.
+        noise: None or float [3, B, P], added to the resampled particles (utils.particle_noise): without it the set collapses onto
+        copies of few ancestors.
+        draw: None or an integer tensor [B] on the device, one random word in [0, 2^32) per env (int32 is read as its bits); None
+        draws them from a torch.Generator the simulator owns, on the device.
+        span: how far below the best S a particle still gets weight, in units of the field (255 per return on an obstacle);
+        1 .. 2^18.  A small span concentrates faster, a large one keeps more hypotheses.
+        Status per env (update.status): 0 ok; 1 fewer than min_points returns; 2 lost -- no particle puts a return on a rewarded
+        cell.  Unless 0 (and with resample=False) the particles come back as they went in and update.pose is NaN.
+        ancestors: also return the input particle every slot was drawn from.
+        Needs StretchSensors.base_lidar in sensors_to_use.
+        The tensors are simulator-owned; update.particles is overwritten by the call after the next one with the same (P, shape)
+        (two sets take turns, so that it can go straight into the next call), the others by the next call."""
+        B, dev = self.num_envs, self.device
+        if not self._read_flags & _lib.READ_LIDAR:
+            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+        if self.nlidar > 1024:
+            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_particles takes 1024")
+        field, grid, sigma, x0y0, cell, frame, ny, nx = self._match_field(field, sigma, origin, cell)
+        try:
+            r_min, r_max = (float(v) for v in range_limits)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("range_limits = (r_min, r_max)") from None
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
+            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
+        if np.float32(r_max) / np.float32(cell) > 8192:
+            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        if (not isinstance(particles, torch.Tensor) or not particles.is_floating_point() or particles.dim() != 3 or particles.shape[0] != 3 or particles.shape[1] != B
+                or not 1 <= particles.shape[2] <= 4096 or particles.device != dev):
+            raise ValueError(f"particles: a float tensor [3, num_envs = {B}, P] on {dev}, 1 <= P <= 4096")
+        P = int(particles.shape[2])
+        if noise is not None and (not isinstance(noise, torch.Tensor) or not noise.is_floating_point() or tuple(noise.shape) != (3, B, P) or noise.device != dev):
+            raise ValueError(f"noise: None or a float tensor [3, num_envs = {B}, P = {P}] on {dev}")
+        if draw is not None and (not isinstance(draw, torch.Tensor) or draw.is_floating_point() or draw.dtype == torch.bool or tuple(draw.shape) != (B,) or draw.device != dev):
+            raise ValueError(f"draw: None or an integer tensor [num_envs = {B}] on {dev}")
+        span, min_points = int(span), int(min_points)
+        if not 1 <= span <= 1 << 18:
+            raise ValueError("span must be in [1, 2^18]")
+        if not 1 <= min_points <= 1024:
+            raise ValueError("min_points must be in [1, 1024]")
+        body, offset = self._base_frame()
+        if offset is not None:
+            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's points cannot be formed in "
+                             "the robot's frame")
+        # every ValueError has been raised: from here on the device works
+        field = self._match_field_tensor(field, grid, sigma)
+        new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
+        bufs = self._cached(self._particles, (P, ny, nx), lambda: dict(out=[new(torch.float32, 3, B, P), new(torch.float32, 3, B, P)], weights=new(torch.int32, B, P),
+                                                                       ancestors=None, stat=new(torch.int32, B, 8), pose=new(torch.float32, 3, B),
+                                                                       draw=new(torch.int32, B)))
+        part_t = particles if particles.dtype == torch.float32 and particles.is_contiguous() else particles.to(torch.float32).contiguous()
+        noise_t = None if noise is None else noise if noise.dtype == torch.float32 and noise.is_contiguous() else noise.to(torch.float32).contiguous()
+        out = bufs["out"][1] if part_t.untyped_storage().data_ptr() == bufs["out"][0].untyped_storage().data_ptr() else bufs["out"][0]   # never the set that goes in
+        if ancestors and bufs["ancestors"] is None:
+            bufs["ancestors"] = new(torch.int32, B, P)
+        anc_t = bufs["ancestors"] if ancestors else None
+        if draw is None:
+            if self._draw_generator is None:
+                self._draw_generator = torch.Generator(device=dev)
+                self._draw_generator.manual_seed(0x5EED)
+            bufs["draw"].copy_(torch.randint(-(1 << 31), 1 << 31, (B,), dtype=torch.int64, device=dev, generator=self._draw_generator))   # the low 32 bits
+        else:
+            bufs["draw"].copy_(draw.to(torch.int64) & 0xFFFFFFFF if draw.dtype != torch.int32 else draw)   # int64 -> int32 keeps the low 32 bits
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self._L.smj_scan_to_particles(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(field), nx, ny, x0y0[0], x0y0[1], cell, vp(part_t), P, vp(noise_t),
+                                           vp(bufs["draw"]), span, min_points, int(bool(resample)), vp(out), vp(bufs["weights"]), vp(anc_t), vp(bufs["stat"]),
+                                           vp(bufs["pose"]), self._stream())
+        _lib.check(self._L, self._ctx, rc, "smj_scan_to_particles")
+        return StatusStretchParticles(time=self._time(), particles=out, weights=bufs["weights"], ancestors=anc_t, stat=bufs["stat"], pose=bufs["pose"], prior=part_t,
+                                      origin=x0y0, cell=cell, frame=frame)
 
     @_require_connection
     def pull_contact_data(self) -> StatusStretchContacts:

@@ -123,6 +123,44 @@ def scan_angles(window: float = 0.1745, step: float = 0.008727, weight: int = 0,
                       bias=torch.tensor(weight * np.abs(k), dtype=torch.int32, device=device))
 
 
+def spread_particles(center, half_extent, num_particles: int, generator=None):
+    """A first particle set for pull_particle_update(): fp32 [3, B, P], uniform in the box center +- half_extent in (x, y, theta).
+    center: a float tensor [3, B] (its device is the result's); half_extent = (metres in x, metres in y, radians), each finite and
+    >= 0; P = num_particles in [1, 4096].  generator: a torch.Generator on that device, None for the global one."""
+    import torch
+
+    if not isinstance(center, torch.Tensor) or not center.is_floating_point() or center.dim() != 2 or center.shape[0] != 3:
+        raise ValueError("center: a float tensor [3, num_envs]")
+    try:
+        half = [float(v) for v in half_extent]
+    except (TypeError, ValueError):
+        raise ValueError("half_extent = (metres in x, metres in y, radians)") from None
+    if len(half) != 3 or not all(np.isfinite(v) and v >= 0 for v in half):
+        raise ValueError("half_extent: three finite numbers >= 0")
+    P = int(num_particles)
+    if not 1 <= P <= 4096:
+        raise ValueError("num_particles must be in [1, 4096]")
+    u = torch.rand(3, center.shape[1], P, dtype=torch.float32, device=center.device, generator=generator) * 2.0 - 1.0
+    return center.to(torch.float32).unsqueeze(2) + u * torch.tensor(half, dtype=torch.float32, device=center.device).reshape(3, 1, 1)
+
+
+def particle_noise(sigma_xy: float, sigma_theta: float, shape, generator=None, device=None):
+    """The noise of pull_particle_update(noise=...) and StatusStretchParticles.predict(noise=...): fp32 of `shape` = (3, B, P), normal
+    with standard deviation sigma_xy [m] in rows x and y and sigma_theta [rad] in row theta.  On the generator's device, or `device`."""
+    import torch
+
+    sigma_xy, sigma_theta = float(sigma_xy), float(sigma_theta)
+    if not (np.isfinite(sigma_xy) and sigma_xy >= 0 and np.isfinite(sigma_theta) and sigma_theta >= 0):
+        raise ValueError("sigma_xy and sigma_theta: finite and >= 0")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or shape[0] != 3:
+        raise ValueError("shape = (3, num_envs, num_particles)")
+    if device is None and generator is not None:
+        device = generator.device
+    n = torch.randn(shape, dtype=torch.float32, device=device, generator=generator)
+    return n * torch.tensor([sigma_xy, sigma_xy, sigma_theta], dtype=torch.float32, device=n.device).reshape(3, 1, 1)
+
+
 def unicycle_pose(v, w, t):
     """Pose (x, y, theta) of a unicycle that starts at the origin facing +x and drives (v, w) for t seconds, fp64, arrays alike:
     (v/w sin(wt), v/w (1 - cos(wt)), wt), written as v t sinc(a) and v t (a/2) sinc(a/2)^2 with a = wt and sinc(a) = sin(a) / a,

@@ -32,6 +32,7 @@
 #include "smj_match.h"
 #include "smj_map.h"
 #include "smj_mcl.h"
+#include "smj_scan.h"
 #include "smj_comm.h"
 static_assert(SMJ_READ_CR == SMJ_READ_CONTACTS && SMJ_CR_WORDS == SMJ_CONTACT_WORDS && SMJ_CR_DIST == SMJ_CON_DIST && SMJ_CR_POS == SMJ_CON_POS &&
                   SMJ_CR_FRAME == SMJ_CON_FRAME && SMJ_CR_FORCE == SMJ_CON_FORCE && SMJ_CR_GEOM1 == SMJ_CON_GEOM1 && SMJ_CR_GEOM2 == SMJ_CON_GEOM2 &&
@@ -152,11 +153,16 @@ static int check_frame(smj_ctx* c, int frame, bool camera_ok, FrameKind* kind) {
   return 0;
 }
 
-static int check_grid(smj_ctx* c, int nx, int ny, int max_cells, float cell, float x0, float y0) {
-  if (nx < 1 || ny < 1 || (long long)nx * ny > max_cells) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, max_cells);
+// the metric placement of a grid: the side of a cell, then the origin
+static int check_origin_cell(smj_ctx* c, float x0, float y0, float cell) {
   if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
   if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
   return 0;
+}
+
+static int check_grid(smj_ctx* c, int nx, int ny, int max_cells, float cell, float x0, float y0) {
+  if (nx < 1 || ny < 1 || (long long)nx * ny > max_cells) return fail(c, -1, "bad grid %d x %d (nx, ny >= 1, nx * ny <= %d)", nx, ny, max_cells);
+  return check_origin_cell(c, x0, y0, cell);
 }
 
 // a grid of integer cells (the distance and navigation entries: no cell size, no origin), within its kernel's limits
@@ -188,6 +194,47 @@ static int check_aligned(smj_ctx* c, std::initializer_list<const void*> ptrs, co
 
 static int check_xpose(smj_ctx* c) {
   return c->state.xpose ? 0 : fail(c, -5, "XPOSE slot is not bound (step with SMJ_READ_POSES first)");
+}
+
+// ---- the entries that read the lidar scan (smj_scan.h).  Each helper stands where its checks stood in every entry, so the order in
+// which an entry's checks fire is the order of its lines.
+// The model has a lidar (`what` ends the refusal: what the entry would have done with the scan) of at most max_rays rays.
+static int check_scan(smj_ctx* c, int max_rays, const char* what) {
+  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to %s", what);
+  return c->render.nlidar <= max_rays ? 0 : fail(c, -1, "the model has %d lidar rays, above %d", c->render.nlidar, max_rays);
+}
+
+static int check_lidar_ld(smj_ctx* c, long lidar_ld) {
+  return lidar_ld >= c->num_envs ? 0 : fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+}
+
+// `tail` ends the refusal of a ray longer than the line arithmetic of smj_occ.h takes
+static int check_range_limits(smj_ctx* c, float r_min, float r_max, float cell, const char* tail) {
+  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
+  return r_max / cell <= (float)SMJ_OCC_MAX_STEPS ? 0 : fail(c, -1, "r_max / cell above %d%s", (int)SMJ_OCC_MAX_STEPS, tail);
+}
+static const char* const RAY_TOO_LONG = ": a ray would cross more cells than the line arithmetic takes";
+static const char* const RAY_BOUND_OF_OCC = ", the bound of smj_lidar_to_occupancy";
+
+// the frame of the entries that work in the robot's frame: a body id
+static int check_robot_frame(smj_ctx* c, int frame) {
+  FrameKind fk;
+  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
+  return check_frame(c, frame, false, &fk);
+}
+
+// The bytes of the scan and of the XPOSE slot that a kernel reads, for check_disjoint.  Either ends with the last env of its last
+// row: the columns beyond num_envs are the caller's, an output may live there.
+static uintptr_t scan_extent(smj_ctx* c, long lidar_ld) {
+  return ((uintptr_t)(c->render.nlidar - 1) * (uintptr_t)lidar_ld + (uintptr_t)c->num_envs) * 4u;
+}
+static uintptr_t xpose_extent(smj_ctx* c) {
+  return ((12u * (uintptr_t)c->model.nbody_all - 1) * (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE] + (uintptr_t)c->num_envs) * 4u;
+}
+
+static SmjScanSource scan_source(smj_ctx* c, const void* lidar_dev, long lidar_ld) {
+  return {c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->render.lidar_site, c->render.site_bodyid, c->render.site_pos, c->render.site_mat,
+          (const float*)lidar_dev, lidar_ld};
 }
 
 // device memory the context allocates at the first call that needs it and keeps (freed in smj_destroy)
@@ -760,20 +807,18 @@ int smj_lidar_to_occupancy(smj_ctx* c, const void* lidar_dev, long lidar_ld, int
                            float r_min, float r_max, int no_return_clears, int accumulate, void* hit_dev, void* miss_dev, void* stream) {
   if (!c) return -1;
   FrameKind fk;
-  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to map");
+  TRY(check_scan(c, 384, "map"));   // (the capacity of the ray cast: smj_create has refused a model with more)
   if (!lidar_dev || !hit_dev) return fail(c, -1, "null scan / hit buffer");
   TRY(check_aligned(c, {lidar_dev, hit_dev, miss_dev}, "scan / hit / miss buffer"));
-  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_lidar_ld(c, lidar_ld));
   TRY(check_grid(c, nx, ny, SMJ_OCC_MAX_CELLS, cell, x0, y0));
-  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
-  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d: a ray would cross more cells than the line arithmetic takes", (int)SMJ_OCC_MAX_STEPS);
+  TRY(check_range_limits(c, r_min, r_max, cell, RAY_TOO_LONG));
   TRY(check_frame(c, frame, false, &fk));
   TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
   const int kind = fk == FRAME_IS_WORLD ? SMJ_OCC_WORLD : SMJ_OCC_BODY;
-  smj_launch_occ(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, c->render.nlidar, c->render.lidar_site, c->render.site_bodyid,
-                 c->render.site_pos, c->render.site_mat, (const float*)lidar_dev, lidar_ld, kind, kind == SMJ_OCC_BODY ? frame : 0, x0, y0, cell,
-                 nx, ny, r_min, r_max, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (hipStream_t)stream);
+  smj_launch_occ(scan_source(c, lidar_dev, lidar_ld), c->num_envs, c->render.nlidar, kind, kind == SMJ_OCC_BODY ? frame : 0, x0, y0, cell, nx, ny, r_min,
+                 r_max, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -855,8 +900,7 @@ int smj_navigation_to_velocity(smj_ctx* c, const void* pose_dev, const void* twi
                     "pose / twist / potential / command / point / bias / cmd / best / score / cell buffer"));
   if ((uintptr_t)score_dev & 7) return fail(c, -1, "score buffer not aligned to 8 bytes");
   TRY(check_cell_grid(c, nx, ny, SMJ_DRIVE_MAX_SIDE, SMJ_DRIVE_MAX_CELLS));
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
+  TRY(check_origin_cell(c, x0, y0, cell));
   if (num_candidates < 1 || num_candidates > SMJ_DRIVE_MAX_CANDIDATES || num_points < 1 || num_points > SMJ_DRIVE_MAX_POINTS ||
       num_candidates * num_points > SMJ_DRIVE_MAX_TABLE)
     return fail(c, -1, "bad table %d x %d (1 <= num_candidates <= %d, 1 <= num_points <= %d, their product <= %d)", num_candidates, num_points,
@@ -886,22 +930,17 @@ int smj_scan_to_pose(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame
                      float y0, float cell, const void* pose_dev, const void* angle_dev, const void* angle_bias_dev, int num_angles, int wx, int wy,
                      int shift_weight, int min_points, void* pose_out_dev, void* best_dev, void* score_dev, void* cell_dev, void* stream) {
   if (!c) return -1;
-  FrameKind fk;
-  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to match");
+  TRY(check_scan(c, SMJ_MATCH_MAX_POINTS, "match"));
   if (!lidar_dev || !field_dev || !pose_dev || !angle_dev || !pose_out_dev || !best_dev)
     return fail(c, -1, "null scan / field / pose / angle / pose_out / best buffer");
   TRY(check_aligned(c, {lidar_dev, pose_dev, angle_dev, angle_bias_dev, pose_out_dev, best_dev, score_dev, cell_dev},
                     "scan / pose / angle / angle_bias / pose_out / best / score / cell buffer"));
   const int nlidar = c->render.nlidar;
-  if (nlidar > SMJ_MATCH_MAX_POINTS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MATCH_MAX_POINTS);
-  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_lidar_ld(c, lidar_ld));
   TRY(check_cell_grid(c, nx, ny, SMJ_MATCH_MAX_SIDE, SMJ_MATCH_MAX_CELLS));
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
-  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
-  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d, the bound of smj_lidar_to_occupancy", (int)SMJ_OCC_MAX_STEPS);
-  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
-  TRY(check_frame(c, frame, false, &fk));
+  TRY(check_origin_cell(c, x0, y0, cell));
+  TRY(check_range_limits(c, r_min, r_max, cell, RAY_BOUND_OF_OCC));
+  TRY(check_robot_frame(c, frame));
   if (num_angles < 1 || num_angles > SMJ_MATCH_MAX_ANGLES) return fail(c, -1, "num_angles %d outside [1, %d]", num_angles, (int)SMJ_MATCH_MAX_ANGLES);
   if (wx < 0 || wx > SMJ_MATCH_MAX_WINDOW || wy < 0 || wy > SMJ_MATCH_MAX_WINDOW)
     return fail(c, -1, "window %d x %d outside [0, %d]", wx, wy, (int)SMJ_MATCH_MAX_WINDOW);
@@ -909,17 +948,14 @@ int smj_scan_to_pose(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame
   if (min_points < 1 || min_points > SMJ_MATCH_MAX_POINTS) return fail(c, -1, "min_points %d outside [1, %d]", min_points, (int)SMJ_MATCH_MAX_POINTS);
   // the workgroup of an env reads its inputs while others store
   const uintptr_t envs = (uintptr_t)c->num_envs, T = (uintptr_t)num_angles, cand = T * (uintptr_t)(2 * wy + 1) * (uintptr_t)(2 * wx + 1);
-  // (the slot's extent ends with the last env of its last row: the columns beyond num_envs are the caller's, an output may live there)
-  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
-  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
+  TRY(check_disjoint(c, {{lidar_dev, scan_extent(c, lidar_ld), "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
                          {pose_dev, envs * 12u, "pose"}, {angle_dev, T * 4u, "angle"}, {angle_bias_dev, T * 4u, "angle_bias"},
-                         {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
+                         {c->state.xpose, xpose_extent(c), "XPOSE slot's"}},
                      {{pose_out_dev, envs * 12u, "pose_out"}, {best_dev, envs * 16u, "best"}, {score_dev, envs * cand * 4u, "score"},
                       {cell_dev, envs * T * (uintptr_t)nlidar * 8u, "cell"}}));
   TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  smj_launch_match(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
-                   c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
+  smj_launch_match(scan_source(c, lidar_dev, lidar_ld), c->num_envs, nlidar, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
                    (const float*)pose_dev, (const float*)angle_dev, (const int*)angle_bias_dev, num_angles, wx, wy, shift_weight, min_points,
                    (float*)pose_out_dev, (int*)best_dev, (int*)score_dev, (int*)cell_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
@@ -932,31 +968,24 @@ int smj_scan_to_map(smj_ctx* c, const void* lidar_dev, long lidar_ld, int frame,
                     float x0, float y0, float cell, int nx, int ny, int no_return_clears, int accumulate, void* hit_dev, void* miss_dev, void* info_dev,
                     void* cell_dev, void* stream) {
   if (!c) return -1;
-  FrameKind fk;
-  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to map");
+  TRY(check_scan(c, SMJ_MAP_MAX_RAYS, "map"));
   if (!lidar_dev || !pose_dev || !hit_dev || !info_dev) return fail(c, -1, "null scan / pose / hit / info buffer");
   TRY(check_aligned(c, {lidar_dev, pose_dev, gate_dev, hit_dev, miss_dev, info_dev, cell_dev}, "scan / pose / gate / hit / miss / info / cell buffer"));
   const int nlidar = c->render.nlidar;
-  if (nlidar > SMJ_MAP_MAX_RAYS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MAP_MAX_RAYS);
-  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_lidar_ld(c, lidar_ld));
   if (gate_ld < 1) return fail(c, -1, "gate_ld %ld below 1", gate_ld);
   TRY(check_cell_grid(c, nx, ny, SMJ_OCC_MAX_CELLS, SMJ_OCC_MAX_CELLS));   // the grids of smj_lidar_to_occupancy: no bound on a side but the cell count
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
-  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
-  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d: a ray would cross more cells than the line arithmetic takes", (int)SMJ_OCC_MAX_STEPS);
-  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
-  TRY(check_frame(c, frame, false, &fk));
+  TRY(check_origin_cell(c, x0, y0, cell));
+  TRY(check_range_limits(c, r_min, r_max, cell, RAY_TOO_LONG));
+  TRY(check_robot_frame(c, frame));
   // the workgroups of an env read its inputs while others store
   const uintptr_t envs = (uintptr_t)c->num_envs, cells = envs * (uintptr_t)nx * (uintptr_t)ny;
-  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
-  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {pose_dev, envs * 12u, "pose"},
-                         {gate_dev, ((envs - 1) * (uintptr_t)gate_ld + 1) * 4u, "gate"}, {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
+  TRY(check_disjoint(c, {{lidar_dev, scan_extent(c, lidar_ld), "scan"}, {pose_dev, envs * 12u, "pose"},
+                         {gate_dev, ((envs - 1) * (uintptr_t)gate_ld + 1) * 4u, "gate"}, {c->state.xpose, xpose_extent(c), "XPOSE slot's"}},
                      {{hit_dev, cells * 4u, "hit"}, {miss_dev, cells * 4u, "miss"}, {info_dev, envs * 16u, "info"}, {cell_dev, envs * (uintptr_t)nlidar * 16u, "cell"}}));
   TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  smj_launch_map(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
-                 c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const float*)pose_dev, (const int*)gate_dev, gate_ld, x0, y0, cell,
+  smj_launch_map(scan_source(c, lidar_dev, lidar_ld), c->num_envs, nlidar, frame, r_min, r_max, (const float*)pose_dev, (const int*)gate_dev, gate_ld, x0, y0, cell,
                  nx, ny, no_return_clears != 0, accumulate != 0, (int*)hit_dev, (int*)miss_dev, (int*)info_dev, (int*)cell_dev, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -969,8 +998,7 @@ int smj_scan_to_particles(smj_ctx* c, const void* lidar_dev, long lidar_ld, int 
                           int min_points, int resample, void* particle_out_dev, void* weight_dev, void* ancestor_dev, void* stat_dev, void* pose_out_dev,
                           void* stream) {
   if (!c) return -1;
-  FrameKind fk;
-  if (!c->has_render || c->render.nlidar < 1) return fail(c, -6, "the model blob carries no lidar / ray-casting tables (sensor_lidar_site, k_lgeom): no scan to weigh particles by");
+  TRY(check_scan(c, SMJ_MCL_MAX_POINTS, "weigh particles by"));
   if (!lidar_dev || !field_dev || !particle_dev || !particle_out_dev || !weight_dev || !stat_dev)
     return fail(c, -1, "null scan / field / particle / particle_out / weight / stat buffer");
   if (resample != 0 && resample != 1) return fail(c, -1, "resample %d is neither 0 nor 1", resample);
@@ -978,30 +1006,24 @@ int smj_scan_to_particles(smj_ctx* c, const void* lidar_dev, long lidar_ld, int 
   TRY(check_aligned(c, {lidar_dev, particle_dev, noise_dev, draw_dev, particle_out_dev, weight_dev, ancestor_dev, stat_dev, pose_out_dev},
                     "scan / particle / noise / draw / particle_out / weight / ancestor / stat / pose_out buffer"));
   const int nlidar = c->render.nlidar;
-  if (nlidar > SMJ_MCL_MAX_POINTS) return fail(c, -1, "the model has %d lidar rays, above %d", nlidar, (int)SMJ_MCL_MAX_POINTS);
-  if (lidar_ld < c->num_envs) return fail(c, -1, "lidar_ld %ld below num_envs %d", lidar_ld, c->num_envs);
+  TRY(check_lidar_ld(c, lidar_ld));
   TRY(check_cell_grid(c, nx, ny, SMJ_MATCH_MAX_SIDE, SMJ_MATCH_MAX_CELLS));
-  if (!(cell > 0.f && cell <= 3.402823466e38f)) return fail(c, -1, "cell must be finite and > 0");
-  if (!(fabsf(x0) <= 3.402823466e38f && fabsf(y0) <= 3.402823466e38f)) return fail(c, -1, "origin not finite");
-  if (!(r_min >= 0.f && r_min <= r_max && r_max <= 3.402823466e38f)) return fail(c, -1, "bad range limits (finite, 0 <= r_min <= r_max)");
-  if (!(r_max / cell <= (float)SMJ_OCC_MAX_STEPS)) return fail(c, -1, "r_max / cell above %d, the bound of smj_lidar_to_occupancy", (int)SMJ_OCC_MAX_STEPS);
-  if (frame < 0) return fail(c, -1, "bad frame %d (a body id: the robot's frame)", frame);
-  TRY(check_frame(c, frame, false, &fk));
+  TRY(check_origin_cell(c, x0, y0, cell));
+  TRY(check_range_limits(c, r_min, r_max, cell, RAY_BOUND_OF_OCC));
+  TRY(check_robot_frame(c, frame));
   if (num_particles < 1 || num_particles > SMJ_MCL_MAX_PARTICLES) return fail(c, -1, "num_particles %d outside [1, %d]", num_particles, (int)SMJ_MCL_MAX_PARTICLES);
   if (span < 1 || span > SMJ_MCL_MAX_SPAN) return fail(c, -1, "span %d outside [1, %d]", span, (int)SMJ_MCL_MAX_SPAN);
   if (min_points < 1 || min_points > SMJ_MCL_MAX_POINTS) return fail(c, -1, "min_points %d outside [1, %d]", min_points, (int)SMJ_MCL_MAX_POINTS);
   // the workgroup of an env reads its inputs while others store
   const uintptr_t envs = (uintptr_t)c->num_envs, words = envs * (uintptr_t)num_particles;
-  const uintptr_t xrows = 12u * (uintptr_t)c->model.nbody_all, ld = (uintptr_t)c->slot_ld[SMJ_SLOT_XPOSE];
-  TRY(check_disjoint(c, {{lidar_dev, ((uintptr_t)(nlidar - 1) * (uintptr_t)lidar_ld + envs) * 4u, "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
+  TRY(check_disjoint(c, {{lidar_dev, scan_extent(c, lidar_ld), "scan"}, {field_dev, envs * (uintptr_t)nx * (uintptr_t)ny, "field"},
                          {particle_dev, words * 12u, "particle"}, {noise_dev, words * 12u, "noise"}, {draw_dev, envs * 4u, "draw"},
-                         {c->state.xpose, ((xrows - 1) * ld + envs) * 4u, "XPOSE slot's"}},
+                         {c->state.xpose, xpose_extent(c), "XPOSE slot's"}},
                      {{particle_out_dev, words * 12u, "particle_out"}, {weight_dev, words * 4u, "weight"}, {ancestor_dev, words * 4u, "ancestor"},
                       {stat_dev, envs * 4u * (uintptr_t)SMJ_MCL_STAT_WORDS, "stat"}, {pose_out_dev, envs * 12u, "pose_out"}}));
   TRY(check_xpose(c));
   HIPCHK(c, hipSetDevice(c->device));
-  smj_launch_mcl(c->state.xpose, c->slot_ld[SMJ_SLOT_XPOSE], c->num_envs, nlidar, c->render.lidar_site, c->render.site_bodyid, c->render.site_pos,
-                 c->render.site_mat, (const float*)lidar_dev, lidar_ld, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
+  smj_launch_mcl(scan_source(c, lidar_dev, lidar_ld), c->num_envs, nlidar, frame, r_min, r_max, (const uint8_t*)field_dev, nx, ny, x0, y0, cell,
                  (const float*)particle_dev, num_particles, (const float*)noise_dev, (const unsigned*)draw_dev, span, min_points, resample,
                  (float*)particle_out_dev, (int*)weight_dev, (int*)ancestor_dev, (int*)stat_dev, (float*)pose_out_dev, c->mcl_stage_field, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());

@@ -72,8 +72,8 @@ SMJ_GRID_HD void smj_map_range(smj_occ_line_t L, int n, smj_hmap_band_t b, int* 
 
 #if defined(__HIPCC__)
 // Launch (smj_map.hip).  gate, miss and cell_out may be null.
-void smj_launch_map(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                    const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const float* pose, const int* gate,
+struct SmjScanSource;   // smj_scan.h
+void smj_launch_map(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const float* pose, const int* gate,
                     long gate_ld, float x0, float y0, float cell, int nx, int ny, int no_return_clears, int accumulate, int* hit, int* miss, int* info,
                     int* cell_out, hipStream_t stream);
 #endif

@@ -1,8 +1,8 @@
 // smj_scan_to_map: the lidar scan and a pose of every env handed in -> per-cell counts of rays that end in a cell (hit) and of rays
 // that pass through it (miss) on a 2-D grid in the frame of that pose (smj_map.h has the status, the line of a ray and the part of a
-// line inside a band; smj_occ.h the ray, the classification and the closed-form line; smj_hmap.h the bands).  One kernel, no global
-// atomics, no workspace: both reductions are integer sums done in LDS and the band is stored once, so the arrays do not depend on
-// any order and two calls give identical bits.
+// line inside a band; smj_occ.h the ray, the classification and the closed-form line; smj_hmap.h the bands; smj_scan.h the source
+// of the rays and the store of a band, with smj_occ.hip).  One kernel, no global atomics, no workspace: both reductions are
+// integer sums done in LDS and the band is stored once, so the arrays do not depend on any order and two calls give identical bits.
 //
 // Grid.  The layout smj_occ.hip measured its way to: one workgroup of 256 threads per (env, band of 4096 cells), the band's cells
 // in LDS as two int32 arrays, ray records built once in LDS by one lane each, groups of 32 lanes per ray, no-return LDS atomics, the
@@ -24,20 +24,14 @@
 // sincosf and the counters show); 0.36 ms with a random half of the envs gated, but 0.56 ms with every other env gated: those
 // workgroups are blocks 4 .. 7 of every eight, which the round-robin deal of blocks puts on four of the eight XCDs.
 #include "smj_map.h"
+#include "smj_scan.h"
 
 static constexpr int MAP_THREADS = 256;
 static constexpr int MAP_GROUP = 32;     // lanes per ray
 static constexpr int MAP_CHUNK = 384;    // ray records in LDS at a time
 
 struct MapArgs {
-  const float* xpose;
-  long ld;
-  const int* lidar_site;
-  const int* site_bodyid;
-  const float* site_pos;
-  const float* site_mat;
-  const float* lidar;
-  long lidar_ld;
+  SmjScanSource src;   // smj_scan.h
   const float* pose;
   const int* gate;
   long gate_ld;
@@ -48,19 +42,6 @@ struct MapArgs {
   int num_envs, nlidar, body, nx, ny, no_return_clears, accumulate, bands;
   float x0, y0, cell, r_min, r_max;
 };
-
-// one int32 array of the band, by the split of smj_hmap.h: lead cells, groups of four, the tail; src null stores zeros
-__device__ __forceinline__ void map_store(int* out, const unsigned* src, int ncell, int tid) {
-  const smj_hmap_split_t s = smj_hmap_store_split((uintptr_t)out, ncell);
-  for (int g = tid; g < s.groups; g += MAP_THREADS) {
-    const int c = s.lead + 4 * g;
-    *reinterpret_cast<int4*>(out + c) = src ? make_int4((int)src[c], (int)src[c + 1], (int)src[c + 2], (int)src[c + 3]) : make_int4(0, 0, 0, 0);
-  }
-  if (tid < s.rest) {   // <= 6 cells
-    const int c = smj_hmap_split_rest(s, tid);
-    out[c] = src ? (int)src[c] : 0;
-  }
-}
 
 // the four words of ray k of cell_dev: one 16-byte store where the buffer allows it
 __device__ __forceinline__ void map_store_cells(int* cell_out, bool wide, int k, int ax, int ay, int bx, int by) {
@@ -91,8 +72,8 @@ __global__ __launch_bounds__(MAP_THREADS) void smj_map_kernel(const MapArgs a) {
   const int status = smj_map_status(x, y, theta, a.gate ? a.gate[(long long)env * a.gate_ld] : 0);
   if (status != SMJ_MAP_OK) {
     if (!a.accumulate) {
-      map_store(ho, nullptr, ncell, tid);
-      if (mo) map_store(mo, nullptr, ncell, tid);
+      smj_scan_store_band<MAP_THREADS, true>(ho, nullptr, ncell, tid);
+      if (mo) smj_scan_store_band<MAP_THREADS, true>(mo, nullptr, ncell, tid);
     }
     if (band == 0 && tid < 4) a.info[4 * env + tid] = tid == SMJ_MAP_INFO_STATUS ? status : 0;
     if (cell_out)
@@ -123,15 +104,16 @@ __global__ __launch_bounds__(MAP_THREADS) void smj_map_kernel(const MapArgs a) {
     // ray records of the chunk
     for (int j = tid; j < count; j += MAP_THREADS) {
       const int k = base + j;
-      const int sid = a.lidar_site[k], sb = a.site_bodyid[sid];
+      const SmjScanSource& s = a.src;
+      const int sid = s.lidar_site[k], sb = s.site_bodyid[sid];
       float bp[3], bm[9], fp[3], fm[9], o[2], d[2], len;
-      for (int q = 0; q < 3; q++) bp[q] = a.xpose[(12 * sb + q) * a.ld + env];
-      for (int q = 0; q < 9; q++) bm[q] = a.xpose[(12 * sb + 3 + q) * a.ld + env];
-      for (int q = 0; q < 3; q++) fp[q] = a.xpose[(12 * a.body + q) * a.ld + env];
-      for (int q = 0; q < 9; q++) fm[q] = a.xpose[(12 * a.body + 3 + q) * a.ld + env];
-      const float lz[3] = {a.site_mat[9 * sid + 2], a.site_mat[9 * sid + 5], a.site_mat[9 * sid + 8]};
-      smj_occ_ray(SMJ_OCC_BODY, bp, bm, a.site_pos + 3 * sid, lz, fp, fm, o, d);
-      const int cls = smj_occ_classify(a.lidar[(long long)k * a.lidar_ld + env], a.r_min, a.r_max, a.no_return_clears, &len);
+      for (int q = 0; q < 3; q++) bp[q] = s.xpose[(12 * sb + q) * s.ld + env];
+      for (int q = 0; q < 9; q++) bm[q] = s.xpose[(12 * sb + 3 + q) * s.ld + env];
+      for (int q = 0; q < 3; q++) fp[q] = s.xpose[(12 * a.body + q) * s.ld + env];
+      for (int q = 0; q < 9; q++) fm[q] = s.xpose[(12 * a.body + 3 + q) * s.ld + env];
+      const float lz[3] = {s.site_mat[9 * sid + 2], s.site_mat[9 * sid + 5], s.site_mat[9 * sid + 8]};
+      smj_occ_ray(SMJ_OCC_BODY, bp, bm, s.site_pos + 3 * sid, lz, fp, fm, o, d);
+      const int cls = smj_occ_classify(s.lidar[(long long)k * s.lidar_ld + env], a.r_min, a.r_max, a.no_return_clears, &len);
       smj_occ_line_t L = smj_map_line(cls, o, d, len, x, y, cs, sn, a.x0, a.y0, a.cell);
       const int word = smj_map_info_word(cls, L.kind);
       nret += word == SMJ_MAP_INFO_RETURNS; nclr += word == SMJ_MAP_INFO_CLEARS; ngrd += word == SMJ_MAP_INFO_GUARDED;
@@ -181,18 +163,16 @@ __global__ __launch_bounds__(MAP_THREADS) void smj_map_kernel(const MapArgs a) {
   __syncthreads();
 
   // (3) store the band once
-  map_store(ho, hits, ncell, tid);
-  if (mo) map_store(mo, misses, ncell, tid);
+  smj_scan_store_band<MAP_THREADS, true>(ho, hits, ncell, tid);
+  if (mo) smj_scan_store_band<MAP_THREADS, true>(mo, misses, ncell, tid);
   if (band == 0 && tid < 4) a.info[4 * env + tid] = tid == SMJ_MAP_INFO_STATUS ? SMJ_MAP_OK : s_info[tid];
 }
 
-void smj_launch_map(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                    const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const float* pose, const int* gate,
+void smj_launch_map(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const float* pose, const int* gate,
                     long gate_ld, float x0, float y0, float cell, int nx, int ny, int no_return_clears, int accumulate, int* hit, int* miss, int* info,
                     int* cell_out, hipStream_t stream) {
   MapArgs a;
-  a.xpose = xpose; a.ld = ld; a.lidar_site = lidar_site; a.site_bodyid = site_bodyid; a.site_pos = site_pos; a.site_mat = site_mat;
-  a.lidar = lidar; a.lidar_ld = lidar_ld; a.pose = pose; a.gate = gate; a.gate_ld = gate_ld;
+  a.src = src; a.pose = pose; a.gate = gate; a.gate_ld = gate_ld;
   a.hit = hit; a.miss = miss; a.info = info; a.cell_out = cell_out;
   a.num_envs = num_envs; a.nlidar = nlidar; a.body = body; a.nx = nx; a.ny = ny; a.no_return_clears = no_return_clears; a.accumulate = accumulate;
   a.bands = smj_hmap_bands(nx, ny, SMJ_OCC_BAND_CELLS);

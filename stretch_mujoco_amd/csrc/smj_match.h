@@ -93,8 +93,8 @@ SMJ_GRID_HD float smj_match_pose_theta(float theta, float angle) { return theta 
 
 #if defined(__HIPCC__)
 // Launch (smj_match.hip).  bias, score and cell_out may be null.
-void smj_launch_match(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                      const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
+struct SmjScanSource;   // smj_scan.h
+void smj_launch_match(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
                       float x0, float y0, float cell, const float* pose, const float* angle, const int* bias, int T, int wx, int wy, int shift_weight,
                       int min_points, float* pose_out, int* best, int* score, int* cell_out, hipStream_t stream);
 #endif

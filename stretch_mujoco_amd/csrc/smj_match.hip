@@ -1,8 +1,9 @@
 // smj_scan_to_pose: the lidar scan, a likelihood field and a prior pose of every env, and one table of rotations shared by all of
 // them -> per env the pose, out of T rotations x (2 wy + 1) x (2 wx + 1) whole-cell shifts, at which the scan's returns collect the
 // largest sum of the field (smj_match.h has the point of a ray, the cell of a point, the score, the order, the status and the output
-// pose).  One kernel, no workspace, no global atomics.  Every output is defined without reference to an order -- an integer sum over
-// the points, the first of a total order over the candidates -- so two calls give identical bits.
+// pose; smj_scan.h what the scan entries share: the source of the rays, the copy of (1) and the butterfly of (3)).  One kernel, no
+// workspace, no global atomics.  Every output is defined without reference to an order -- an integer sum over the points, the first
+// of a total order over the candidates -- so two calls give identical bits.
 //
 // Grid.  One workgroup of 512 threads per env.
 //   (1) the env's field goes into LDS once, bytes as they are: the copy starts at the LDS offset that has the alignment of the global
@@ -25,19 +26,13 @@
 // return), 5.0 ms when every ray returns; 5.4 ms before the list of placed points; 3.0 / 1.6 / 1.4 / 1.3 ms with 128 / 256 / 448 / 512
 // threads (the sums wait on LDS: more waves hide more of it, and 441 candidates fill 512 threads in one round).
 #include "smj_match.h"
+#include "smj_scan.h"
 
 static constexpr int MATCH_THREADS = 512;
 static constexpr int MATCH_SMALL_CELLS = 16384;
 
 struct MatchArgs {
-  const float* xpose;
-  long ld;
-  const int* lidar_site;
-  const int* site_bodyid;
-  const float* site_pos;
-  const float* site_mat;
-  const float* lidar;
-  long lidar_ld;
+  SmjScanSource src;   // smj_scan.h
   const uint8_t* field;
   const float* pose;
   const float* angle;
@@ -63,17 +58,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void smj_match_kernel(const MatchArg
   const float x = a.pose[env], y = a.pose[a.num_envs + env], theta = a.pose[2 * a.num_envs + env];
 
   // (1) the field: LDS byte sh + i holds field byte i, and sh + lead is a multiple of 16 in both address spaces
-  const uint8_t* g = a.field + (long long)env * ncell;
-  const int sh = (int)((uintptr_t)g & 15);
-  const uint8_t* field = s_raw + sh;
-  {
-    uint8_t* dst = s_raw + sh;
-    const int lead = min((16 - sh) & 15, ncell), groups = (ncell - lead) >> 4, tail = lead + 16 * groups;
-    for (int i = tid; i < lead; i += MATCH_THREADS) dst[i] = g[i];
-    for (int q = tid; q < groups; q += MATCH_THREADS)
-      *reinterpret_cast<uint4*>(dst + lead + 16 * q) = *reinterpret_cast<const uint4*>(g + lead + 16 * q);
-    for (int i = tail + tid; i < ncell; i += MATCH_THREADS) dst[i] = g[i];
-  }
+  const uint8_t* field = smj_scan_stage_field<MATCH_THREADS>(s_raw, a.field + (long long)env * ncell, ncell, tid);
   if (tid == 0) { s_n = 0; s_m[0] = 0; }
   if (tid < T) {
     float s, c;
@@ -84,15 +69,16 @@ __global__ __launch_bounds__(MATCH_THREADS) void smj_match_kernel(const MatchArg
   __syncthreads();
   // the points
   for (int k = tid; k < K; k += MATCH_THREADS) {
-    const int sid = a.lidar_site[k], sb = a.site_bodyid[sid];
+    const SmjScanSource& s = a.src;
+    const int sid = s.lidar_site[k], sb = s.site_bodyid[sid];
     float bp[3], bm[9], fp[3], fm[9], o[2], d[2], p[2], len;
-    for (int j = 0; j < 3; j++) bp[j] = a.xpose[(12 * sb + j) * a.ld + env];
-    for (int j = 0; j < 9; j++) bm[j] = a.xpose[(12 * sb + 3 + j) * a.ld + env];
-    for (int j = 0; j < 3; j++) fp[j] = a.xpose[(12 * a.body + j) * a.ld + env];
-    for (int j = 0; j < 9; j++) fm[j] = a.xpose[(12 * a.body + 3 + j) * a.ld + env];
-    const float lz[3] = {a.site_mat[9 * sid + 2], a.site_mat[9 * sid + 5], a.site_mat[9 * sid + 8]};
-    smj_occ_ray(SMJ_OCC_BODY, bp, bm, a.site_pos + 3 * sid, lz, fp, fm, o, d);
-    const int cls = smj_occ_classify(a.lidar[(long long)k * a.lidar_ld + env], a.r_min, a.r_max, 0, &len);
+    for (int j = 0; j < 3; j++) bp[j] = s.xpose[(12 * sb + j) * s.ld + env];
+    for (int j = 0; j < 9; j++) bm[j] = s.xpose[(12 * sb + 3 + j) * s.ld + env];
+    for (int j = 0; j < 3; j++) fp[j] = s.xpose[(12 * a.body + j) * s.ld + env];
+    for (int j = 0; j < 9; j++) fm[j] = s.xpose[(12 * a.body + 3 + j) * s.ld + env];
+    const float lz[3] = {s.site_mat[9 * sid + 2], s.site_mat[9 * sid + 5], s.site_mat[9 * sid + 8]};
+    smj_occ_ray(SMJ_OCC_BODY, bp, bm, s.site_pos + 3 * sid, lz, fp, fm, o, d);
+    const int cls = smj_occ_classify(s.lidar[(long long)k * s.lidar_ld + env], a.r_min, a.r_max, 0, &len);
     smj_match_point(o, d, len, p);
     const bool counts = cls == SMJ_OCC_RETURN && smj_drive_finite(p[0]) && smj_drive_finite(p[1]);
     s_px[k] = counts ? p[0] : __int_as_float(0x7fc00000);
@@ -137,10 +123,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void smj_match_kernel(const MatchArg
   }
 
   // (3) the first in the order: within the wave, then across the waves
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int oJ = __shfl_xor(mineJ, off), oi = __shfl_xor(minei, off);
-    if (smj_match_before(oJ, oi, mineJ, minei)) { mineJ = oJ; minei = oi; }
-  }
+  const int2 first = smj_scan_wave_first(mineJ, minei);
+  mineJ = first.x; minei = first.y;
   if ((tid & 63) == 0) {
     s_bestJ[tid >> 6] = mineJ;
     s_besti[tid >> 6] = minei;
@@ -164,13 +148,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void smj_match_kernel(const MatchArg
   }
 }
 
-void smj_launch_match(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                      const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
+void smj_launch_match(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
                       float x0, float y0, float cell, const float* pose, const float* angle, const int* bias, int T, int wx, int wy, int shift_weight,
                       int min_points, float* pose_out, int* best, int* score, int* cell_out, hipStream_t stream) {
   MatchArgs a;
-  a.xpose = xpose; a.ld = ld; a.lidar_site = lidar_site; a.site_bodyid = site_bodyid; a.site_pos = site_pos; a.site_mat = site_mat;
-  a.lidar = lidar; a.lidar_ld = lidar_ld; a.field = field; a.pose = pose; a.angle = angle; a.bias = bias;
+  a.src = src; a.field = field; a.pose = pose; a.angle = angle; a.bias = bias;
   a.pose_out = pose_out; a.best = best; a.score = score; a.cell_out = cell_out;
   a.num_envs = num_envs; a.nlidar = nlidar; a.body = body; a.nx = nx; a.ny = ny; a.T = T; a.wx = wx; a.wy = wy;
   a.shift_weight = shift_weight; a.min_points = min_points;

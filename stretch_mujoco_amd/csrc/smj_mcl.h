@@ -72,8 +72,8 @@ SMJ_GRID_HD int smj_mcl_status(int n, int min_points, int s_max) {
 #if defined(__HIPCC__)
 // Launch (smj_mcl.hip).  noise, draw (when resample = 0), ancestor and pose_out may be null.  stage_field: the env's field is copied
 // into LDS (0: gathered from global memory through L2).
-void smj_launch_mcl(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                    const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
+struct SmjScanSource;   // smj_scan.h
+void smj_launch_mcl(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
                     float x0, float y0, float cell, const float* particle, int P, const float* noise, const unsigned* draw, int span, int min_points,
                     int resample, float* particle_out, int* weight, int* ancestor, int* stat, float* pose_out, int stage_field, hipStream_t stream);
 #endif

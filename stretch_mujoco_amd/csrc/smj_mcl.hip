@@ -1,12 +1,13 @@
-// smj_scan_to_particles: the lidar scan, a likelihood field and P particles of every env -> per particle the sum S of the field under
-// the scan's returns laid out from that particle, the best particle, and (status OK, resample != 0) a systematic resampling of the
-// particles by w = max(S - cut, 0) (smj_mcl.h has the weight of a point, cut and w, the threshold of a slot, the ancestor search,
-// the effective sample size and the status; smj_match.h the point of a ray and its cell).  One kernel, no workspace, no global
-// atomics.  Every output is defined without reference to an order -- integer sums, the first of a total order, a search on integer
-// sums -- so two calls give identical bits.
+// smj_scan_to_particles: the lidar scan, a likelihood field and P particles of every env -> per particle the sum S of the field
+// under the scan's returns laid out from that particle, the best particle, and (status OK, resample != 0) a systematic resampling of
+// the particles by w = max(S - cut, 0) (smj_mcl.h has the weight of a point, cut and w, the threshold of a slot, the ancestor
+// search, the effective sample size and the status; smj_match.h the point of a ray and its cell; smj_scan.h the source of the rays,
+// the copy of (1) and the butterfly of (3), with smj_match.hip).  One kernel, no workspace, no global atomics.  Every output is
+// defined without reference to an order -- integer sums, the first of a total order, a search on integer sums -- so two calls give
+// identical bits.
 //
 // Grid.  One workgroup of 512 threads per env.
-//   (1) the env's field goes into LDS once, bytes as they are, by the copy of smj_match.hip (the LDS offset takes the alignment of
+//   (1) the env's field goes into LDS once, bytes as they are, by the copy of smj_scan.h (the LDS offset takes the alignment of
 //       the global address, so the middle moves in 16-byte loads whatever the pointer).  Thread k turns ray k into its point of the
 //       robot's frame and, if it counts, appends it to a list in LDS (an LDS atomic hands out the slots; the order of the list does
 //       not show in an integer sum): the sums run over the returns alone;
@@ -32,20 +33,14 @@
 // "mcl_stage_field").  The walk is bound by the arithmetic of smj_match_cell, about 35 vector instructions per particle and point:
 // 1.24 T look-ups/s; smj_scan_to_pose's default search (9261 lattice poses) takes 1.28 ms beside it.
 #include "smj_mcl.h"
+#include "smj_scan.h"
 
 static constexpr int MCL_THREADS = 512;
 static constexpr int MCL_WAVES = MCL_THREADS / 64;
 static constexpr int MCL_SMALL_CELLS = 16384;
 
 struct MclArgs {
-  const float* xpose;
-  long ld;
-  const int* lidar_site;
-  const int* site_bodyid;
-  const float* site_pos;
-  const float* site_mat;
-  const float* lidar;
-  long lidar_ld;
+  SmjScanSource src;   // smj_scan.h
   const uint8_t* field;
   const float* particle;
   const float* noise;
@@ -92,29 +87,21 @@ __global__ __launch_bounds__(MCL_THREADS) void smj_mcl_kernel(const MclArgs a) {
   // (1) the field: LDS byte sh + i holds field byte i, and sh + lead is a multiple of 16 in both address spaces
   const uint8_t* g = a.field + (long long)env * ncell;
   const uint8_t* field = g;
-  if (CELLS > 0) {
-    const int sh = (int)((uintptr_t)g & 15);
-    uint8_t* dst = s_raw + sh;
-    const int lead = min((16 - sh) & 15, ncell), groups = (ncell - lead) >> 4, tail = lead + 16 * groups;
-    for (int i = tid; i < lead; i += MCL_THREADS) dst[i] = g[i];
-    for (int q = tid; q < groups; q += MCL_THREADS)
-      *reinterpret_cast<uint4*>(dst + lead + 16 * q) = *reinterpret_cast<const uint4*>(g + lead + 16 * q);
-    for (int i = tail + tid; i < ncell; i += MCL_THREADS) dst[i] = g[i];
-    field = dst;
-  }
+  if (CELLS > 0) field = smj_scan_stage_field<MCL_THREADS>(s_raw, g, ncell, tid);
   if (tid == 0) { s_n = 0; s_distinct = 0; s_sq = 0ull; }
   __syncthreads();
   // the points
   for (int k = tid; k < K; k += MCL_THREADS) {
-    const int sid = a.lidar_site[k], sb = a.site_bodyid[sid];
+    const SmjScanSource& s = a.src;
+    const int sid = s.lidar_site[k], sb = s.site_bodyid[sid];
     float bp[3], bm[9], fp[3], fm[9], o[2], d[2], p[2], len;
-    for (int j = 0; j < 3; j++) bp[j] = a.xpose[(12 * sb + j) * a.ld + env];
-    for (int j = 0; j < 9; j++) bm[j] = a.xpose[(12 * sb + 3 + j) * a.ld + env];
-    for (int j = 0; j < 3; j++) fp[j] = a.xpose[(12 * a.body + j) * a.ld + env];
-    for (int j = 0; j < 9; j++) fm[j] = a.xpose[(12 * a.body + 3 + j) * a.ld + env];
-    const float lz[3] = {a.site_mat[9 * sid + 2], a.site_mat[9 * sid + 5], a.site_mat[9 * sid + 8]};
-    smj_occ_ray(SMJ_OCC_BODY, bp, bm, a.site_pos + 3 * sid, lz, fp, fm, o, d);
-    const int cls = smj_occ_classify(a.lidar[(long long)k * a.lidar_ld + env], a.r_min, a.r_max, 0, &len);
+    for (int j = 0; j < 3; j++) bp[j] = s.xpose[(12 * sb + j) * s.ld + env];
+    for (int j = 0; j < 9; j++) bm[j] = s.xpose[(12 * sb + 3 + j) * s.ld + env];
+    for (int j = 0; j < 3; j++) fp[j] = s.xpose[(12 * a.body + j) * s.ld + env];
+    for (int j = 0; j < 9; j++) fm[j] = s.xpose[(12 * a.body + 3 + j) * s.ld + env];
+    const float lz[3] = {s.site_mat[9 * sid + 2], s.site_mat[9 * sid + 5], s.site_mat[9 * sid + 8]};
+    smj_occ_ray(SMJ_OCC_BODY, bp, bm, s.site_pos + 3 * sid, lz, fp, fm, o, d);
+    const int cls = smj_occ_classify(s.lidar[(long long)k * s.lidar_ld + env], a.r_min, a.r_max, 0, &len);
     smj_match_point(o, d, len, p);
     if (cls == SMJ_OCC_RETURN && smj_drive_finite(p[0]) && smj_drive_finite(p[1])) s_p[atomicAdd(&s_n, 1)] = make_float2(p[0], p[1]);   // LDS, at most K slots
   }
@@ -140,10 +127,8 @@ __global__ __launch_bounds__(MCL_THREADS) void smj_mcl_kernel(const MclArgs a) {
   }
 
   // (3) the first in the order: within the wave, then across the waves
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int oS = __shfl_xor(mineS, off), oj = __shfl_xor(minej, off);
-    if (smj_match_before(oS, oj, mineS, minej)) { mineS = oS; minej = oj; }
-  }
+  const int2 first = smj_scan_wave_first(mineS, minej);
+  mineS = first.x; minej = first.y;
   if ((tid & 63) == 0) {
     s_bestS[tid >> 6] = mineS;
     s_bestj[tid >> 6] = minej;
@@ -223,13 +208,11 @@ __global__ __launch_bounds__(MCL_THREADS) void smj_mcl_kernel(const MclArgs a) {
                                              : tid == SMJ_MCL_STAT_ESS ? smj_mcl_ess(total, (uint64_t)s_sq) : tid == SMJ_MCL_STAT_CUT ? cut : s_distinct;
 }
 
-void smj_launch_mcl(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid, const float* site_pos,
-                    const float* site_mat, const float* lidar, long lidar_ld, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
+void smj_launch_mcl(const SmjScanSource& src, int num_envs, int nlidar, int body, float r_min, float r_max, const uint8_t* field, int nx, int ny,
                     float x0, float y0, float cell, const float* particle, int P, const float* noise, const unsigned* draw, int span, int min_points,
                     int resample, float* particle_out, int* weight, int* ancestor, int* stat, float* pose_out, int stage_field, hipStream_t stream) {
   MclArgs a;
-  a.xpose = xpose; a.ld = ld; a.lidar_site = lidar_site; a.site_bodyid = site_bodyid; a.site_pos = site_pos; a.site_mat = site_mat;
-  a.lidar = lidar; a.lidar_ld = lidar_ld; a.field = field; a.particle = particle; a.noise = noise; a.draw = draw;
+  a.src = src; a.field = field; a.particle = particle; a.noise = noise; a.draw = draw;
   a.particle_out = particle_out; a.weight = weight; a.ancestor = ancestor; a.stat = stat; a.pose_out = pose_out;
   a.num_envs = num_envs; a.nlidar = nlidar; a.body = body; a.nx = nx; a.ny = ny; a.P = P; a.span = span; a.min_points = min_points;
   a.resample = resample;

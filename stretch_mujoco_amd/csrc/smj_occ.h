@@ -103,8 +103,7 @@ SMJ_PT_HD int smj_occ_layer(smj_occ_line_t L, int n, int i) { return L.kind == S
 
 #if defined(__HIPCC__)
 // Launch (smj_occ.hip).  kind / body: SMJ_OCC_* and, for SMJ_OCC_BODY, the fused body; miss may be null.
-void smj_launch_occ(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid,
-                    const float* site_pos, const float* site_mat, const float* lidar, long lidar_ld, int kind, int body, float x0, float y0,
-                    float cell, int nx, int ny, float r_min, float r_max, int no_return_clears, int accumulate, int* hit, int* miss,
-                    hipStream_t stream);
+struct SmjScanSource;   // smj_scan.h
+void smj_launch_occ(const SmjScanSource& src, int num_envs, int nlidar, int kind, int body, float x0, float y0, float cell, int nx, int ny,
+                    float r_min, float r_max, int no_return_clears, int accumulate, int* hit, int* miss, hipStream_t stream);
 #endif

@@ -1,7 +1,8 @@
 // smj_lidar_to_occupancy: the lidar scan -> per-cell counts of rays that end in a cell (hit) and of rays that pass through it (miss)
 // on a 2-D grid in the world or a body frame (smj_occ.h has the ray, the classification and the closed-form line; smj_hmap.h the
-// bands).  One kernel, no global atomics, no workspace: both reductions are integer sums done in LDS and the band is stored once,
-// so the arrays do not depend on any order and two calls give identical bits.
+// bands; smj_scan.h what the scan entries share: the source of the rays and the store of a band).  One kernel, no global atomics, no
+// workspace: both reductions are integer sums done in LDS and the band is stored once, so the arrays do not depend on any order and
+// two calls give identical bits.
 //
 // Grid.  One workgroup per (env, band).  The band's cells live in LDS as two int32 arrays.  The workgroup (1) sets its cells to zero,
 // or with accumulate to what the outputs hold, while thread k turns ray k into a record in LDS: the pose of the site's body and of
@@ -36,38 +37,19 @@
 // (0.25 / 0.88 ms to 9.5 m): the walk evaluates the cells a ray has outside the band before it skips them.  The closed form would give
 // the i-range inside a band directly; that is not done here.
 #include "smj_occ.h"
+#include "smj_scan.h"
 
 static constexpr int OCC_THREADS = 256;
 static constexpr int OCC_GROUP = 32;        // lanes per ray
 static constexpr int OCC_MAX_RAYS = 384;    // the capacity of smj_lidar_kernel (smj_create refuses a model with more)
 
 struct OccArgs {
-  const float* xpose;
-  long ld;
-  const int* lidar_site;
-  const int* site_bodyid;
-  const float* site_pos;
-  const float* site_mat;
-  const float* lidar;
-  long lidar_ld;
+  SmjScanSource src;   // smj_scan.h
   int* hit;
   int* miss;
   int nlidar, kind, body, nx, ny, no_return_clears, accumulate, bands;
   float x0, y0, inv_cell, r_min, r_max;
 };
-
-// one int32 array of the band, by the split of smj_hmap.h: lead cells, groups of four, the tail
-__device__ __forceinline__ void occ_store(int* out, const unsigned* src, int ncell, int tid) {
-  const smj_hmap_split_t s = smj_hmap_store_split((uintptr_t)out, ncell);
-  for (int g = tid; g < s.groups; g += OCC_THREADS) {
-    const int c = s.lead + 4 * g;
-    *reinterpret_cast<int4*>(out + c) = make_int4((int)src[c], (int)src[c + 1], (int)src[c + 2], (int)src[c + 3]);
-  }
-  if (tid < s.rest) {   // <= 6 cells
-    const int c = smj_hmap_split_rest(s, tid);
-    out[c] = (int)src[c];
-  }
-}
 
 __global__ __launch_bounds__(OCC_THREADS) void smj_occ_kernel(const OccArgs a) {
   __shared__ unsigned hits[SMJ_OCC_BAND_CELLS];
@@ -94,17 +76,18 @@ __global__ __launch_bounds__(OCC_THREADS) void smj_occ_kernel(const OccArgs a) {
     }
   }
   for (int k = tid; k < a.nlidar; k += OCC_THREADS) {
-    const int sid = a.lidar_site[k], sb = a.site_bodyid[sid];
+    const SmjScanSource& s = a.src;
+    const int sid = s.lidar_site[k], sb = s.site_bodyid[sid];
     float bp[3], bm[9], fp[3] = {}, fm[9] = {}, o[2], d[2], len;
-    for (int j = 0; j < 3; j++) bp[j] = a.xpose[(12 * sb + j) * a.ld + env];
-    for (int j = 0; j < 9; j++) bm[j] = a.xpose[(12 * sb + 3 + j) * a.ld + env];
+    for (int j = 0; j < 3; j++) bp[j] = s.xpose[(12 * sb + j) * s.ld + env];
+    for (int j = 0; j < 9; j++) bm[j] = s.xpose[(12 * sb + 3 + j) * s.ld + env];
     if (a.kind == SMJ_OCC_BODY) {
-      for (int j = 0; j < 3; j++) fp[j] = a.xpose[(12 * a.body + j) * a.ld + env];
-      for (int j = 0; j < 9; j++) fm[j] = a.xpose[(12 * a.body + 3 + j) * a.ld + env];
+      for (int j = 0; j < 3; j++) fp[j] = s.xpose[(12 * a.body + j) * s.ld + env];
+      for (int j = 0; j < 9; j++) fm[j] = s.xpose[(12 * a.body + 3 + j) * s.ld + env];
     }
-    const float lz[3] = {a.site_mat[9 * sid + 2], a.site_mat[9 * sid + 5], a.site_mat[9 * sid + 8]};
-    smj_occ_ray(a.kind, bp, bm, a.site_pos + 3 * sid, lz, fp, fm, o, d);
-    const int cls = smj_occ_classify(a.lidar[(long long)k * a.lidar_ld + env], a.r_min, a.r_max, a.no_return_clears, &len);
+    const float lz[3] = {s.site_mat[9 * sid + 2], s.site_mat[9 * sid + 5], s.site_mat[9 * sid + 8]};
+    smj_occ_ray(a.kind, bp, bm, s.site_pos + 3 * sid, lz, fp, fm, o, d);
+    const int cls = smj_occ_classify(s.lidar[(long long)k * s.lidar_ld + env], a.r_min, a.r_max, a.no_return_clears, &len);
     smj_occ_line_t L = smj_occ_line(cls, o, d, len, a.x0, a.y0, a.inv_cell);
     // the line stays inside the box of its two ends: a ray whose box misses the band adds nothing here
     const int xl = min(L.ax, L.bx), xh = max(L.ax, L.bx), yl = min(L.ay, L.by), yh = max(L.ay, L.by);
@@ -139,17 +122,14 @@ __global__ __launch_bounds__(OCC_THREADS) void smj_occ_kernel(const OccArgs a) {
   __syncthreads();
 
   // (3) store the band once
-  occ_store(ho, hits, ncell, tid);
-  if (mo) occ_store(mo, misses, ncell, tid);
+  smj_scan_store_band<OCC_THREADS, false>(ho, hits, ncell, tid);
+  if (mo) smj_scan_store_band<OCC_THREADS, false>(mo, misses, ncell, tid);
 }
 
-void smj_launch_occ(const float* xpose, long ld, int num_envs, int nlidar, const int* lidar_site, const int* site_bodyid,
-                    const float* site_pos, const float* site_mat, const float* lidar, long lidar_ld, int kind, int body, float x0, float y0,
-                    float cell, int nx, int ny, float r_min, float r_max, int no_return_clears, int accumulate, int* hit, int* miss,
-                    hipStream_t stream) {
+void smj_launch_occ(const SmjScanSource& src, int num_envs, int nlidar, int kind, int body, float x0, float y0, float cell, int nx, int ny,
+                    float r_min, float r_max, int no_return_clears, int accumulate, int* hit, int* miss, hipStream_t stream) {
   OccArgs a;
-  a.xpose = xpose; a.ld = ld; a.lidar_site = lidar_site; a.site_bodyid = site_bodyid; a.site_pos = site_pos; a.site_mat = site_mat;
-  a.lidar = lidar; a.lidar_ld = lidar_ld; a.hit = hit; a.miss = miss;
+  a.src = src; a.hit = hit; a.miss = miss;
   a.nlidar = nlidar; a.kind = kind; a.body = body; a.nx = nx; a.ny = ny; a.no_return_clears = no_return_clears; a.accumulate = accumulate;
   a.bands = smj_hmap_bands(nx, ny, SMJ_OCC_BAND_CELLS);
   a.x0 = x0; a.y0 = y0; a.inv_cell = 1.f / cell; a.r_min = r_min; a.r_max = r_max;

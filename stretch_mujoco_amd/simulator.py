@@ -30,6 +30,19 @@ from .glue import Glue
 _MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 
 
+def vp(t):
+    """The device pointer of a tensor as the C-ABI takes it; None stays None (an optional buffer left out)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check_range_limits(r_min, r_max, cell):
+    """What every entry that reads the scan asks of its range limits once they are floats."""
+    if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
+        raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
+    if np.float32(r_max) / np.float32(cell) > 8192:
+        raise ValueError("range_limits[1] / cell must not exceed 8192")
+
+
 def _require_connection(fn):
     def wrapper(self, *a, **k):
         if not self.is_running():
@@ -356,6 +369,24 @@ class StretchBatchSimulator:
             return self._base_frame()
         return (_lib.FRAME_CAMERA if frame == "camera" else _lib.FRAME_WORLD), None
 
+    def _need_lidar(self):
+        if not self._read_flags & _lib.READ_LIDAR:
+            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+
+    def _need_scan(self, entry):
+        """The head of the entries that take the scan in the robot's frame: the readout is on, the scan is one `entry` takes."""
+        self._need_lidar()
+        if self.nlidar > 1024:
+            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: {entry} takes 1024")
+
+    def _robot_body(self, what):
+        """The body whose frame is the robot's, for the same entries; `what` of the scan cannot be formed when base_link is offset in it."""
+        body, offset = self._base_frame()
+        if offset is not None:
+            raise ValueError(f"base_link sits at a non-identity fixed pose inside its fused body: the scan's {what} cannot be formed in "
+                             "the robot's frame")
+        return body
+
     @staticmethod
     def _grid_args(shape, origin, cell, pair, pair_doc):
         """(ny, nx, x0, y0, cell, lo, hi) of a binned map, checked; `pair` is the entry's own interval (z_range, range_limits)."""
@@ -526,14 +557,10 @@ class StretchBatchSimulator:
         r_max / cell <= 8192.  accumulate=True adds to the buffers instead of overwriting them: in the world frame that maps across
         steps.  Needs StretchSensors.base_lidar in sensors_to_use.
         The tensors are simulator-owned and overwritten (or added to) by the next call with the same (frame, shape)."""
-        if not self._read_flags & _lib.READ_LIDAR:
-            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
+        self._need_lidar()
         fr, offset = self._frame_id(frame, ("world", "base"))
         ny, nx, x0, y0, cell, r_min, r_max = self._grid_args(shape, origin, cell, range_limits, "range_limits = (r_min, r_max)")
-        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
-            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
-        if np.float32(r_max) / np.float32(cell) > 8192:
-            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        _check_range_limits(r_min, r_max, cell)
         if offset is not None:
             raise ValueError('frame "base": base_link sits at a non-identity fixed pose inside its fused body; a binned grid cannot be '
                              'corrected afterwards (use frame="world")')
@@ -755,7 +782,6 @@ class StretchBatchSimulator:
             hit, miss = bufs[4], bufs[5]
         if cost is not None:
             cost = cost.to(device=dev).contiguous()
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
         rc = self._L.smj_occupancy_to_frontiers(self._ctx, vp(hit), vp(miss), vp(cost) if cost is not None else None, nx, ny, min_hits, lethal,
                                                 min_size, G, vp(bufs[0]), vp(bufs[1]), vp(bufs[2]), vp(bufs[3]), self._stream())
         _lib.check(self._L, self._ctx, rc, "smj_occupancy_to_frontiers")
@@ -878,7 +904,6 @@ class StretchBatchSimulator:
             cost = cost.to(device=dev).contiguous()
         command, points = command.to(dev).contiguous(), points.to(dev).contiguous()
         bias = bias.to(dev).contiguous() if bias is not None else None
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         score_t, cells_t = (bufs["score"] if scores else None), (bufs["cells"] if cells else None)
         rc = self._L.smj_navigation_to_velocity(self._ctx, vp(pose_t), vp(twist_t), vp(cost), vp(pot), nx, ny, x0y0[0], x0y0[1], cell, vp(command), vp(points),
                                                 vp(bias), K, P, lethal, int(bool(outside_is_free)), goal_weight, obstacle_weight, arrive, max_dv, max_dw,
@@ -950,20 +975,14 @@ class StretchBatchSimulator:
         from .utils import ScanAngles, scan_angles
 
         B, dev = self.num_envs, self.device
-        if not self._read_flags & _lib.READ_LIDAR:
-            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
-        if self.nlidar > 1024:
-            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_pose takes 1024")
+        self._need_scan("smj_scan_to_pose")
         field, grid, sigma, x0y0, cell, frame, ny, nx = self._match_field(field, sigma, origin, cell)
         try:
             r_min, r_max = (float(v) for v in range_limits)
             wx, wy = (int(round(float(v) / cell)) for v in window)
         except (TypeError, ValueError, OverflowError):
             raise ValueError("range_limits = (r_min, r_max), window = (metres in x, metres in y)") from None
-        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
-            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
-        if np.float32(r_max) / np.float32(cell) > 8192:
-            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        _check_range_limits(r_min, r_max, cell)
         if not (0 <= wx <= 32 and 0 <= wy <= 32):
             raise ValueError("window: 0 <= round(window / cell) <= 32 cells on either side")
         min_points, shift_weight = int(min_points), int(shift_weight)
@@ -985,10 +1004,7 @@ class StretchBatchSimulator:
             raise ValueError(f"angles: bias None or int32 [T = {T}]")
         if prior is not None and (not isinstance(prior, torch.Tensor) or not prior.is_floating_point() or tuple(prior.shape) != (3, B)):
             raise ValueError(f"prior: None or a float tensor [3, num_envs = {B}]")
-        body, offset = self._base_frame()
-        if offset is not None:
-            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's points cannot be formed in "
-                             "the robot's frame")
+        body = self._robot_body("points")
         # every ValueError has been raised: from here on the device works
         field = self._match_field_tensor(field, grid, sigma)
         new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
@@ -1007,7 +1023,6 @@ class StretchBatchSimulator:
             prior_t = self.base_pose
         ang = ang.to(dev).contiguous()
         bias = bias.to(dev).contiguous() if bias is not None else None
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         score_t, cells_t = (bufs["score"] if scores else None), (bufs["cells"] if cells else None)
         rc = self._L.smj_scan_to_pose(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(field), nx, ny, x0y0[0], x0y0[1], cell, vp(prior_t), vp(ang),
                                       vp(bias), T, wx, wy, shift_weight, min_points, vp(bufs["pose"]), vp(bufs["best"]), vp(score_t), vp(cells_t),
@@ -1038,10 +1053,7 @@ class StretchBatchSimulator:
         Needs StretchSensors.base_lidar in sensors_to_use.
         The tensors are simulator-owned and overwritten (the map: added to) by the next call with the same shape."""
         B, dev = self.num_envs, self.device
-        if not self._read_flags & _lib.READ_LIDAR:
-            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
-        if self.nlidar > 1024:
-            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_map takes 1024")
+        self._need_scan("smj_scan_to_map")
         if not isinstance(pose, torch.Tensor) or not pose.is_floating_point() or tuple(pose.shape) != (3, B) or pose.device != dev:
             raise ValueError(f"pose: a float tensor [3, num_envs = {B}] on {dev}")
         if grid is None:
@@ -1061,10 +1073,7 @@ class StretchBatchSimulator:
             ny, nx, x0, y0, cell, r_min, r_max = self._grid_args(hit.shape[1:], (x0, y0), cell, range_limits, "range_limits = (r_min, r_max)")
         if frame not in ("world", "grid"):
             raise ValueError('the grid\'s frame must be "world" or "grid": a "base" grid moves with the robot and is no map')
-        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
-            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
-        if np.float32(r_max) / np.float32(cell) > 8192:
-            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        _check_range_limits(r_min, r_max, cell)
         gate_t, gate_at, gate_ld = None, None, 1
         if isinstance(gate, StatusStretchScanMatch):
             gate_t = gate.best
@@ -1075,10 +1084,7 @@ class StretchBatchSimulator:
             if not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or tuple(gate.shape) != (B,) or gate.device != dev or (B > 1 and gate.stride(0) < 1):
                 raise ValueError(f"gate: None, an int32 tensor [num_envs = {B}] on {dev}, or a StatusStretchScanMatch")
             gate_t, gate_at, gate_ld = gate, gate.data_ptr(), max(int(gate.stride(0)), 1)
-        body, offset = self._base_frame()
-        if offset is not None:
-            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's rays cannot be formed in "
-                             "the robot's frame")
+        body = self._robot_body("rays")
         # every ValueError has been raised: from here on the device works
         new = lambda *shape: torch.empty(B, *shape, dtype=torch.int32, device=dev)
         bufs = self._cached(self._maps, (ny, nx), lambda: dict(hit=None, miss=None, info=new(4), cells=None))
@@ -1090,7 +1096,6 @@ class StretchBatchSimulator:
             bufs["cells"] = new(self.nlidar, 4)
         cells_t = bufs["cells"] if cells else None
         pose_t = pose if pose.dtype == torch.float32 and pose.is_contiguous() else pose.to(torch.float32).contiguous()
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         rc = self._L.smj_scan_to_map(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(pose_t), ctypes.c_void_p(gate_at) if gate_at is not None else None, gate_ld,
                                      x0, y0, cell, nx, ny, int(bool(no_return_clears)), int(bool(accumulate)), vp(hit), vp(miss), vp(bufs["info"]), vp(cells_t),
                                      self._stream())
@@ -1129,19 +1134,13 @@ class StretchBatchSimulator:
         The tensors are simulator-owned; update.particles is overwritten by the call after the next one with the same (P, shape)
         (two sets take turns, so that it can go straight into the next call), the others by the next call."""
         B, dev = self.num_envs, self.device
-        if not self._read_flags & _lib.READ_LIDAR:
-            raise _lib.SmjError("the lidar readout is off: put StretchSensors.base_lidar into sensors_to_use")
-        if self.nlidar > 1024:
-            raise _lib.SmjError(f"the model has {self.nlidar} lidar rays: smj_scan_to_particles takes 1024")
+        self._need_scan("smj_scan_to_particles")
         field, grid, sigma, x0y0, cell, frame, ny, nx = self._match_field(field, sigma, origin, cell)
         try:
             r_min, r_max = (float(v) for v in range_limits)
         except (TypeError, ValueError, OverflowError):
             raise ValueError("range_limits = (r_min, r_max)") from None
-        if not (np.isfinite(r_min) and np.isfinite(r_max) and 0 <= r_min <= r_max):
-            raise ValueError("range_limits: finite, 0 <= r_min <= r_max")
-        if np.float32(r_max) / np.float32(cell) > 8192:
-            raise ValueError("range_limits[1] / cell must not exceed 8192")
+        _check_range_limits(r_min, r_max, cell)
         if (not isinstance(particles, torch.Tensor) or not particles.is_floating_point() or particles.dim() != 3 or particles.shape[0] != 3 or particles.shape[1] != B
                 or not 1 <= particles.shape[2] <= 4096 or particles.device != dev):
             raise ValueError(f"particles: a float tensor [3, num_envs = {B}, P] on {dev}, 1 <= P <= 4096")
@@ -1155,10 +1154,7 @@ class StretchBatchSimulator:
             raise ValueError("span must be in [1, 2^18]")
         if not 1 <= min_points <= 1024:
             raise ValueError("min_points must be in [1, 1024]")
-        body, offset = self._base_frame()
-        if offset is not None:
-            raise ValueError("base_link sits at a non-identity fixed pose inside its fused body: the scan's points cannot be formed in "
-                             "the robot's frame")
+        body = self._robot_body("points")
         # every ValueError has been raised: from here on the device works
         field = self._match_field_tensor(field, grid, sigma)
         new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
@@ -1178,7 +1174,6 @@ class StretchBatchSimulator:
             bufs["draw"].copy_(torch.randint(-(1 << 31), 1 << 31, (B,), dtype=torch.int64, device=dev, generator=self._draw_generator))   # the low 32 bits
         else:
             bufs["draw"].copy_(draw.to(torch.int64) & 0xFFFFFFFF if draw.dtype != torch.int32 else draw)   # int64 -> int32 keeps the low 32 bits
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         rc = self._L.smj_scan_to_particles(self._ctx, vp(self.lidar), B, body, r_min, r_max, vp(field), nx, ny, x0y0[0], x0y0[1], cell, vp(part_t), P, vp(noise_t),
                                            vp(bufs["draw"]), span, min_points, int(bool(resample)), vp(out), vp(bufs["weights"]), vp(anc_t), vp(bufs["stat"]),
                                            vp(bufs["pose"]), self._stream())

@@ -1,5 +1,6 @@
 // What the host check programs of the device headers share (tests/{points,hmap,occ,edt,nav}/*_check.cpp): the CHECK macro with its
-// failure counter, the special floats and bit casts, a pose of fp32 numbers with a seeded random one, the cover of the store groups.
+// failure counter, the special floats and bit casts, a pose of fp32 numbers with a seeded random one, the cover of the store groups,
+// the cover of the field copy's split.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -49,4 +50,29 @@ static void check_store_groups(Groups groups, First first) {
         for (int k = 0; k < groups(n); k++) holders += first(k, al) <= c && c < first(k, al) + 4;
         CHECK(holders == 1, "groups of %d cells al %d: cell %d in %d groups", n, al, c, holders);
       }
+}
+
+// The split of the copy of an env's byte field into LDS (csrc/smj_scan.h, handed in): for every alignment 0 .. 15 of the global
+// address and every ncell = 0 .. CELLS, each byte is copied exactly once (lead bytes, groups of 16, the tail), every group starts on
+// a multiple of 16 in both address spaces (LDS byte sh + i holds byte i), and the copy stays within s_raw[CELLS + 16].
+template <int CELLS, class Split>
+static void check_stage_split(Split split) {
+  for (int al = 0; al < 16; al++)
+    for (int ncell = 0; ncell <= CELLS; ncell++) {
+      const uintptr_t g = 0x7f3c5000u + (uintptr_t)al;
+      const auto s = split(g, ncell);
+      int copies[CELLS + 16] = {};
+      CHECK(s.sh == al && s.lead >= 0 && s.lead < 16 && s.lead <= ncell && s.groups >= 0 && s.tail == s.lead + 16 * s.groups && s.tail <= ncell && ncell - s.tail < 16,
+            "split of %d bytes at alignment %d: sh %d lead %d groups %d tail %d", ncell, al, s.sh, s.lead, s.groups, s.tail);
+      for (int i = 0; i < s.lead && i < CELLS + 16; i++) copies[i]++;
+      for (int q = 0; q < s.groups; q++) {
+        const int first = s.lead + 16 * q;
+        CHECK((g + (uintptr_t)first) % 16 == 0 && (s.sh + first) % 16 == 0, "group %d of %d bytes at alignment %d starts off a boundary", q, ncell, al);
+        for (int i = first; i < first + 16 && i < CELLS + 16; i++) copies[i]++;
+      }
+      for (int i = s.tail; i < ncell; i++) copies[i]++;
+      for (int i = 0; i < CELLS + 16; i++)
+        CHECK(copies[i] == (i < ncell), "%d bytes at alignment %d: byte %d copied %d times", ncell, al, i, copies[i]);
+      CHECK(ncell == 0 || s.sh + ncell - 1 < CELLS + 16, "%d bytes at alignment %d leave the LDS array", ncell, al);
+    }
 }

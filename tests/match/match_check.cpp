@@ -4,8 +4,10 @@
 // emulation of the kernel with the kernel's own functions -- the placed points of a rotation as a list of packed words, the candidates of a rotation
 // dealt to 64, 128, 256 or 512 threads with per-thread firsts, the butterfly over a wave's 64 lanes and the pass over the waves -- held
 // against the harness's own loops, written from the public header's text, on seeded fields from a small set of values, so that equal
-// scores are the rule.  Windows 0, 1, 3, 32, rotation counts 1, 5, 64, grids from 1 x 1.  Prints the number of cases and "ok".
+// scores are the rule.  Windows 0, 1, 3, 32, rotation counts 1, 5, 64, grids from 1 x 1.  Before those, the split of the field's copy
+// into LDS (csrc/smj_scan.h) at every alignment.  Prints the number of cases and "ok".
 #include "smj_match.h"
+#include "smj_scan.h"
 #include "host_check.h"
 
 #include <algorithm>
@@ -192,6 +194,8 @@ int main() {
           smj_occ_classify(NaN, 0.2f, 5.0f, 0, &len) == SMJ_OCC_DROP && smj_occ_classify(0.1f, 0.2f, 5.0f, 0, &len) == SMJ_OCC_DROP &&
           smj_occ_classify(INF, 0.2f, 5.0f, 0, &len) == SMJ_OCC_DROP, "only a return counts");
   }
+
+  check_stage_split<48>(smj_scan_stage_split);      // the copy of the field into LDS, phase (1)
 
   // ---- the kernel's phases against the loops
   std::mt19937 g(20261);

@@ -8,6 +8,7 @@
 // against the harness's own loops, written from the public header's text, on seeded sums from a small set of values, so that equal
 // sums and particles of weight 0 are the rule.  P from 1 to 4096, not only multiples of 64.  Prints the number of cases and "ok".
 #include "smj_mcl.h"
+#include "smj_scan.h"
 #include "host_check.h"
 
 #include <algorithm>
@@ -164,6 +165,8 @@ static Case random_case(std::mt19937& g, int P, int flavour) {
 }
 
 int main() {
+  check_stage_split<48>(smj_scan_stage_split);      // the copy of the field into LDS, the staged builds' phase (1)
+
   // ---- the functions on their own
   CHECK(smj_mcl_cut(91800, 4096) == 87704 && smj_mcl_cut(4096, 4096) == 0 && smj_mcl_cut(100, 4096) == 0 && smj_mcl_cut(0, 1) == 0 && smj_mcl_cut(261120, 1) == 261119 &&
         smj_mcl_cut(261120, 1 << 18) == 0, "cut");

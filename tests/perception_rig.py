@@ -1,11 +1,14 @@
 """The scene the GPU tests of the perception entries share (tests/test_gpu_{point_cloud,height_map,occupancy,distance,navigation}.py):
 stretch_scene, three envs driven apart, 200 steps.  Each test module keeps its own module-scoped fixture, which calls build() with
 its cameras and sensors (lidar_rig() for the lidar's entries), adds what only it needs and stops the simulator after its yield;
-bare_context() is the whole body of the `bare` fixtures.  Below those: the small helpers of the C calls, the guarded output buffers."""
+bare_context() is the whole body of the `bare` fixtures.  scan_rig() is lidar_rig() with what the modules of the scan entries share
+(tests/test_gpu_{scanmatch,mapping,localize}.py), which also import the `bare` fixture from here.  Below those: the small helpers of
+the C calls, the guarded output buffers."""
 import ctypes
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from conftest import ROOT
@@ -78,6 +81,39 @@ def lidar_rig():
     return build(sensors=[StretchSensors.base_lidar])
 
 
+def scan_rig(nlidar):
+    """lidar_rig() with the inputs of the scan entries: .geoms, per env (o, d, So, Sd) of the rays in the robot's frame, from the XPOSE
+    array and the site tables; the synthetic scan of scanmatch_ref.float_stage_inputs on them (.scan_host, .pts, .mar) and its device
+    copy .scan.  Computed once per module and left unchanged."""
+    import occupancy_ref
+    import scanmatch_ref
+    from point_cloud_ref import body_pose
+
+    r = lidar_rig()
+    sim = r.sim
+    assert sim.nlidar == nlidar
+    sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
+    site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
+    site_pos = to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
+    lz = to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
+    poses = {b: body_pose(r.xpose, int(b)) for b in set(site_body.tolist()) | {r.base}}
+    r.geoms = []
+    for e in range(B):
+        bp = np.stack([poses[int(b)][0][e] for b in site_body])
+        bm = np.stack([poses[int(b)][1][e] for b in site_body])
+        r.geoms.append(occupancy_ref.ray_geometry(bp, bm, site_pos, lz, poses[r.base][0][e], poses[r.base][1][e]))
+    r.scan_host, r.pts, r.mar = scanmatch_ref.float_stage_inputs(r.geoms)
+    r.scan = dev(r.scan_host)
+    return r
+
+
+def rig_scans(r, poses):
+    """fp32 scans [K, B] cast in the room of scanmatch_ref along the scan rig's own rays from poses [B, 3]."""
+    import scanmatch_ref
+
+    return np.stack([scanmatch_ref.room_scan(poses[e], r.geoms[e][0], r.geoms[e][1]) for e in range(B)], 1).astype(np.float32)
+
+
 def bare_context():
     """Fixture body: smj_create on the stretch_scene blob, B envs, NOTHING bound; .cache is the module's.  Destroyed at teardown."""
     from stretch_mujoco_amd import lib
@@ -90,6 +126,15 @@ def bare_context():
     yield b
     torch.cuda.synchronize()
     b.L.smj_destroy(b.ctx)
+
+
+@pytest.fixture(scope="module")
+def bare():
+    yield from bare_context()
+
+
+def dev(a):
+    return torch.tensor(np.ascontiguousarray(a), device=DEV)
 
 
 def ptr(t):
@@ -112,17 +157,23 @@ def sentinels(ny, nx, fill=-7):
 
 class Guarded:
     """An int32 output [B, ny, nx] as .view, `pad` words into a buffer of -12345 with 37 more behind it (pad 36: on a 16-byte boundary,
-    37: four bytes past one).  check(): the guards are untouched and the view equals `want`."""
+    37: four bytes past one); Guarded.of(pad, dtype, *shape) for an output of another type and shape.  check(): the guards are
+    untouched and the view equals `want` (floats byte for byte, so a NaN equals itself and -0 is not +0)."""
 
-    def __init__(self, pad, ny, nx):
-        self.pad, self.cells = pad, B * ny * nx
-        self.big = torch.full((pad + self.cells + 37,), -12345, dtype=torch.int32, device=DEV)
-        self.view = self.big[pad:pad + self.cells].view(B, ny, nx)
-        assert self.view.data_ptr() % 16 == (4 * pad) % 16
+    def __init__(self, pad, ny, nx, dtype=torch.int32, shape=None):
+        shape = (B, ny, nx) if shape is None else shape
+        self.pad, self.cells = pad, int(np.prod(shape))
+        self.big = torch.full((pad + self.cells + 37,), -12345, dtype=dtype, device=DEV)
+        self.view = self.big[pad:pad + self.cells].view(*shape)
+        assert self.view.data_ptr() % 16 == (self.big.element_size() * pad) % 16
+
+    @classmethod
+    def of(cls, pad, dtype, *shape):
+        return cls(pad, None, None, dtype, shape)
 
     def check(self, want):
         assert (self.big[:self.pad] == -12345).all() and (self.big[self.pad + self.cells:] == -12345).all()
-        assert torch.equal(self.view, want)
+        assert self.view.cpu().numpy().tobytes() == want.cpu().numpy().tobytes() if self.view.is_floating_point() else torch.equal(self.view, want)
 
 
 def frame_id(r, frame):

@@ -18,12 +18,10 @@ import torch
 
 import localize_ref as ref
 import mapping_ref
-import occupancy_ref
 import perception_rig
 import scanmatch_ref
 from conftest import ROOT
-from perception_rig import B, DEV, Guarded
-from point_cloud_ref import body_pose
+from perception_rig import B, DEV, Guarded, bare, dev as _dev, rig_scans as _rig_scans, stream as _stream  # noqa: F401 (bare: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,37 +40,10 @@ SPANS = (1, 4096, 1 << 18)
 
 @pytest.fixture(scope="module")
 def rig():
-    r = perception_rig.lidar_rig()
-    sim = r.sim
-    assert sim.nlidar == K
-    sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
-    site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
-    site_pos = perception_rig.to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
-    lz = perception_rig.to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
-    poses = {b: body_pose(r.xpose, int(b)) for b in set(site_body.tolist()) | {r.base}}
-    r.geoms = []      # per env (o, d, So, Sd) of the rays in the robot's frame, from the XPOSE array and the site tables
-    for e in range(B):
-        bp = np.stack([poses[int(b)][0][e] for b in site_body])
-        bm = np.stack([poses[int(b)][1][e] for b in site_body])
-        r.geoms.append(occupancy_ref.ray_geometry(bp, bm, site_pos, lz, poses[r.base][0][e], poses[r.base][1][e]))
-    r.scan_host, r.pts, r.mar = scanmatch_ref.float_stage_inputs(r.geoms)
-    r.scan = _dev(r.scan_host)
+    r = perception_rig.scan_rig(K)
     r.n = [int(np.isfinite(r.pts[e]).all(-1).sum()) for e in range(B)]      # the counting rays
     yield r
-    sim.stop()
-
-
-@pytest.fixture(scope="module")
-def bare():
-    yield from perception_rig.bare_context()
-
-
-def _dev(a):
-    return torch.tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _stream():
-    return perception_rig.stream()
+    r.sim.stop()
 
 
 def _field(nx, ny, seed=1):
@@ -338,11 +309,6 @@ def test_error_codes_and_a_refused_call_writes_nothing(rig, bare):
     assert words("stat").view(B, 8).tolist() == [[-1, 0, 0, ref.FEW, 0, 0, 0, 0]] * B and bool((words("pose") == 0x7FC00000).all())
     assert words("anc").view(B, P).tolist() == [list(range(P))] * B
     assert all(int(words(name).abs().max()) == 0 for name in ("scan", "field", "particle", "noise", "draw", "out", "weight"))      # the inputs are unchanged
-
-
-def _rig_scans(r, poses):
-    """fp32 scans [K, B] cast in the room along the rig's own rays from poses [B, 3]."""
-    return np.stack([scanmatch_ref.room_scan(poses[e], r.geoms[e][0], r.geoms[e][1]) for e in range(B)], 1).astype(np.float32)
 
 
 def test_the_status_gates_the_mapping_entry_where_it_lies(rig):

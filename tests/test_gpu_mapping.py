@@ -22,8 +22,7 @@ import occupancy_ref
 import perception_rig
 import scanmatch_ref
 from conftest import ROOT
-from perception_rig import B, DEV, Guarded
-from point_cloud_ref import body_pose
+from perception_rig import B, DEV, Guarded, bare, dev as _dev, rig_scans as _rig_scans, stream as _stream  # noqa: F401 (bare: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,38 +39,11 @@ GRIDS = [(128, 96, (-3.187, -2.379), CELL), (37, 29, (-0.913, -0.707), CELL), (1
 
 @pytest.fixture(scope="module")
 def rig():
-    r = perception_rig.lidar_rig()
-    sim = r.sim
-    assert sim.nlidar == K
-    sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
-    site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
-    site_pos = perception_rig.to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
-    lz = perception_rig.to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
-    poses = {b: body_pose(r.xpose, int(b)) for b in set(site_body.tolist()) | {r.base}}
-    r.geoms = []      # per env (o, d, So, Sd) of the rays in the robot's frame, from the XPOSE array and the site tables
-    for e in range(B):
-        bp = np.stack([poses[int(b)][0][e] for b in site_body])
-        bm = np.stack([poses[int(b)][1][e] for b in site_body])
-        r.geoms.append(occupancy_ref.ray_geometry(bp, bm, site_pos, lz, poses[r.base][0][e], poses[r.base][1][e]))
-    r.scan_host, r.pts, r.mar = scanmatch_ref.float_stage_inputs(r.geoms)
-    r.scan = _dev(r.scan_host)
+    r = perception_rig.scan_rig(K)
     r.prior = np.ascontiguousarray(FS.prior.T)                            # [3, B] fp32
     r.truth = np.ascontiguousarray(FS.truth.T.astype(np.float32))
     yield r
-    sim.stop()
-
-
-@pytest.fixture(scope="module")
-def bare():
-    yield from perception_rig.bare_context()
-
-
-def _dev(a):
-    return torch.tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _stream():
-    return perception_rig.stream()
+    r.sim.stop()
 
 
 def _outputs(nx, ny, fill=FILL):
@@ -359,11 +331,6 @@ def test_error_codes_and_a_refused_call_writes_nothing(rig, bare):
     # all-zero inputs: every range 0 is below r_min (or a return of length 0 with r_min = 0), the pose (0, 0, 0), the gate open
     assert words("info").view(B, 4)[:, 0].tolist() == [ref.OK] * B
     assert all(int(words(name).abs().max()) == 0 for name in ("scan", "pose", "gate"))      # the inputs are unchanged
-
-
-def _rig_scans(r, poses):
-    """fp32 scans [K, B] cast in the room along the rig's own rays from poses [B, 3]."""
-    return np.stack([scanmatch_ref.room_scan(poses[e], r.geoms[e][0], r.geoms[e][1]) for e in range(B)], 1).astype(np.float32)
 
 
 def test_the_loop_closes_on_the_device(rig):

@@ -14,11 +14,10 @@ import numpy as np
 import pytest
 import torch
 
-import occupancy_ref
 import perception_rig
 import scanmatch_ref as ref
 from conftest import ROOT
-from perception_rig import B, DEV, f32, to32
+from perception_rig import B, DEV, Guarded, bare, dev as _dev, f32, stream as _stream  # noqa: F401 (bare: the module's fixture)
 from point_cloud_ref import body_pose
 
 pytestmark = pytest.mark.gpu
@@ -33,37 +32,10 @@ LIMITS = ref.FLOAT_STAGE.limits
 
 @pytest.fixture(scope="module")
 def rig():
-    r = perception_rig.lidar_rig()
-    sim = r.sim
-    assert sim.nlidar == K
-    sites = np.asarray(sim.model["sensor_lidar_site"]).reshape(-1)
-    site_body = np.asarray(sim.model["site_bodyid"]).reshape(-1)[sites]
-    site_pos = to32(np.asarray(sim.model["site_pos"]).reshape(-1, 3)[sites])
-    lz = to32(np.asarray(sim.model["k_site_mat"]).reshape(-1, 3, 3)[sites][:, :, 2])
-    poses = {b: body_pose(r.xpose, int(b)) for b in set(site_body.tolist()) | {r.base}}
-    r.geoms = []      # per env (o, d, So, Sd) of the rays in the robot's frame, from the XPOSE array and the site tables
-    for e in range(B):
-        bp = np.stack([poses[int(b)][0][e] for b in site_body])
-        bm = np.stack([poses[int(b)][1][e] for b in site_body])
-        r.geoms.append(occupancy_ref.ray_geometry(bp, bm, site_pos, lz, poses[r.base][0][e], poses[r.base][1][e]))
-    r.scan_host, r.pts, r.mar = ref.float_stage_inputs(r.geoms)
-    r.scan = _dev(r.scan_host)
+    r = perception_rig.scan_rig(K)
     r.prior = np.ascontiguousarray(ref.FLOAT_STAGE.prior.T)
     yield r
-    sim.stop()
-
-
-@pytest.fixture(scope="module")
-def bare():
-    yield from perception_rig.bare_context()
-
-
-def _dev(a):
-    return torch.tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _stream():
-    return perception_rig.stream()
+    r.sim.stop()
 
 
 def _outputs(T, wx, wy):
@@ -230,19 +202,6 @@ def test_null_score_and_cell_are_left_untouched(rig):
         assert torch.equal(got[3], full[3]) if cells else int((got[3] != FILL).sum()) == 0
 
 
-class _Guarded:
-    """An output of `shape` and `dtype` as .view, `pad` elements into a buffer of sentinels with 9 more behind it."""
-
-    def __init__(self, pad, dtype, *shape):
-        self.pad, self.n = pad, int(np.prod(shape))
-        self.big = torch.full((pad + self.n + 9,), -12345, dtype=dtype, device=DEV)
-        self.view = self.big[pad:pad + self.n].view(*shape)
-
-    def check(self, want):
-        assert (self.big[:self.pad] == -12345).all() and (self.big[self.pad + self.n:] == -12345).all()
-        assert self.view.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
-
-
 def _shifted(t, fill, by):
     big = torch.full((t.numel() + by + 21,), fill, dtype=t.dtype, device=DEV)
     view = big[by:by + t.numel()].view(t.shape)
@@ -265,8 +224,8 @@ def test_nothing_outside_the_outputs_is_written_and_alignment_does_not_matter(ri
     results, fields = [], []
     for moved, by, pads in ((False, 1, (1, 1, 1, 1)), (True, 2, (1, 1, 1, 1)), (False, 3, (2, 3, 2, 3)), (True, 7, (3, 2, 3, 2)), (False, 8, (2, 1, 3, 1)), (True, 13, (1, 3, 1, 2)),
                             (False, 15, (3, 3, 2, 1)), (True, 16, (2, 2, 2, 2))):
-        outs = [_Guarded(32 + pads[0], torch.float32, 3, B), _Guarded(32 + pads[1], torch.int32, B, 4), _Guarded(32 + pads[2], torch.int32, B, T, 2 * wy + 1, 2 * wx + 1),
-                _Guarded(32 + pads[3], torch.int32, B, T, K, 2)]
+        outs = [Guarded.of(32 + pads[0], torch.float32, 3, B), Guarded.of(32 + pads[1], torch.int32, B, 4), Guarded.of(32 + pads[2], torch.int32, B, T, 2 * wy + 1, 2 * wx + 1),
+                Guarded.of(32 + pads[3], torch.int32, B, T, K, 2)]
         fbig, fview = _shifted(field, 99, by)
         scan, pr, an, bi = [v for _, v in ins] if moved else (r.scan, prior, angles, bias)
         _match(r, scan, fview, pr, an, origin=origin, wx=wx, wy=wy, bias=bi, sw=1, out=[o.view for o in outs])

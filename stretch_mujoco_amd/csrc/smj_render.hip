@@ -13,6 +13,7 @@
 #include "smj_render.h"
 #include "smj_bvh.h"   // SMJ_BVH_LEAF
 #include "smj_meshlet.h"   // SMJ_MESHLET_TRIS / _VERTS
+#include "smj_ray.h"   // RT_*, ray_prim, ray_prim_any
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,8 +42,6 @@ struct RGeom {
   float pos[3], mat[9], cen[3], rbound, size[3];
   int type, rmesh, gid;
 };
-
-enum { RT_PLANE = 0, RT_SPHERE = 2, RT_CAPSULE = 3, RT_ELLIPSOID = 4, RT_CYLINDER = 5, RT_BOX = 6, RT_MESH = 7 };
 
 __device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }   // 1-ulp reciprocal (the rasteriser's paths: depths are compared at 1e-4)
@@ -142,170 +141,6 @@ __device__ float ray_mesh(const DevRender& R, int rmesh, const float* o, const f
   return best;
 }
 
-// entering intersection of the ray with a primitive in its own frame (outside faces only), or -1
-__device__ float ray_prim(int type, const float* size, const float* lp, const float* lv, float tnear) {
-  if (type == RT_PLANE) {
-    if (lv[2] > -1e-15f) return -1.f;
-    const float x = -lp[2] / lv[2];
-    if (x < tnear) return -1.f;
-    const float px = lp[0] + x * lv[0], py = lp[1] + x * lv[1];
-    if ((size[0] <= 0 || fabsf(px) <= size[0]) && (size[1] <= 0 || fabsf(py) <= size[1])) return x;
-    return -1.f;
-  }
-  if (type == RT_SPHERE) {
-    const float a = dot3(lv, lv), b = dot3(lv, lp), c = dot3(lp, lp) - size[0] * size[0];
-    const float det = b * b - a * c;
-    if (det < 1e-15f) return -1.f;
-    const float x = (-b - sqrtf(det)) / a;
-    return x >= tnear ? x : -1.f;
-  }
-  if (type == RT_CYLINDER) {
-    float best = -1.f;
-    const float a = lv[0] * lv[0] + lv[1] * lv[1], b = lv[0] * lp[0] + lv[1] * lp[1], c = lp[0] * lp[0] + lp[1] * lp[1] - size[0] * size[0];
-    const float det = b * b - a * c;
-    if (a > 1e-15f && det >= 1e-15f) {
-      const float x = (-b - sqrtf(det)) / a;
-      if (x >= tnear && fabsf(lp[2] + x * lv[2]) <= size[1]) best = x;
-    }
-    if (fabsf(lv[2]) > 1e-15f) {
-      const float sg = lv[2] < 0 ? 1.f : -1.f;   // the cap facing the ray
-      const float x = (sg * size[1] - lp[2]) / lv[2];
-      if (x >= tnear) {
-        const float px = lp[0] + x * lv[0], py = lp[1] + x * lv[1];
-        if (px * px + py * py <= size[0] * size[0] && (best < 0 || x < best)) best = x;
-      }
-    }
-    return best;
-  }
-  if (type == RT_BOX) {
-    float best = -1.f;
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-      if (fabsf(lv[ax]) < 1e-15f) continue;
-      const float sg = lv[ax] < 0 ? 1.f : -1.f;   // the face of this axis that faces the ray
-      const float x = (sg * size[ax] - lp[ax]) / lv[ax];
-      if (x < tnear) continue;
-      const int a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
-      if (fabsf(lp[a1] + x * lv[a1]) <= size[a1] && fabsf(lp[a2] + x * lv[a2]) <= size[a2] && (best < 0 || x < best)) best = x;
-    }
-    return best;
-  }
-  if (type == RT_CAPSULE) {
-    float best = -1.f;
-    const float a = lv[0] * lv[0] + lv[1] * lv[1], b = lv[0] * lp[0] + lv[1] * lp[1], c = lp[0] * lp[0] + lp[1] * lp[1] - size[0] * size[0];
-    const float det = b * b - a * c;
-    if (a > 1e-15f && det >= 1e-15f) {
-      const float x = (-b - sqrtf(det)) / a;
-      if (x >= tnear && fabsf(lp[2] + x * lv[2]) <= size[1]) best = x;
-    }
-    for (int sg = -1; sg <= 1; sg += 2) {
-      const float q[3] = {lp[0], lp[1], lp[2] - sg * size[1]};
-      const float aa = dot3(lv, lv), bb = dot3(lv, q), cc = dot3(q, q) - size[0] * size[0];
-      const float dd = bb * bb - aa * cc;
-      if (dd < 1e-15f) continue;
-      const float x = (-bb - sqrtf(dd)) / aa;
-      if (x >= tnear && sg * (lp[2] + x * lv[2]) >= size[1] && (best < 0 || x < best)) best = x;
-    }
-    return best;
-  }
-  if (type == RT_ELLIPSOID) {
-    const float s[3] = {1.f / size[0], 1.f / size[1], 1.f / size[2]};
-    const float v[3] = {lv[0] * s[0], lv[1] * s[1], lv[2] * s[2]}, p[3] = {lp[0] * s[0], lp[1] * s[1], lp[2] * s[2]};
-    const float a = dot3(v, v), b = dot3(v, p), c = dot3(p, p) - 1.f;
-    const float det = b * b - a * c;
-    if (det < 1e-15f) return -1.f;
-    const float x = (-b - sqrtf(det)) / a;
-    return x >= tnear ? x : -1.f;
-  }
-  return -1.f;
-}
-
-
-// nearest intersection (either side) of a ray with a primitive in its own frame, or -1.  [MJ] mj_rayGeom
-__device__ float ray_quad(float a, float b, float c) {
-  float det = b * b - a * c;
-  if (det < 1e-15f) return -1.f;
-  det = sqrtf(det);
-  const float x0 = (-b - det) / a, x1 = (-b + det) / a;
-  if (x0 >= 0) return x0;
-  if (x1 >= 0) return x1;
-  return -1.f;
-}
-__device__ float ray_prim_any(int type, const float* size, const float* lp, const float* lv) {
-  if (type == RT_PLANE) {
-    if (lv[2] > -1e-15f) return -1.f;
-    const float x = -lp[2] / lv[2];
-    if (x < 0) return -1.f;
-    const float px = lp[0] + x * lv[0], py = lp[1] + x * lv[1];
-    if ((size[0] <= 0 || fabsf(px) <= size[0]) && (size[1] <= 0 || fabsf(py) <= size[1])) return x;
-    return -1.f;
-  }
-  if (type == RT_SPHERE) return ray_quad(dot3(lv, lv), dot3(lv, lp), dot3(lp, lp) - size[0] * size[0]);
-  if (type == RT_CYLINDER) {
-    float best = -1.f;
-    const float a = lv[0] * lv[0] + lv[1] * lv[1], b = lv[0] * lp[0] + lv[1] * lp[1], c = lp[0] * lp[0] + lp[1] * lp[1] - size[0] * size[0];
-    if (a > 1e-15f) {
-      const float x = ray_quad(a, b, c);
-      if (x >= 0 && fabsf(lp[2] + x * lv[2]) <= size[1]) best = x;
-    }
-    if (fabsf(lv[2]) > 1e-15f)
-      for (int sg = -1; sg <= 1; sg += 2) {
-        const float x = (sg * size[1] - lp[2]) / lv[2];
-        if (x >= 0) {
-          const float px = lp[0] + x * lv[0], py = lp[1] + x * lv[1];
-          if (px * px + py * py <= size[0] * size[0] && (best < 0 || x < best)) best = x;
-        }
-      }
-    return best;
-  }
-  if (type == RT_BOX) {
-    float best = -1.f;
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-      if (fabsf(lv[ax]) < 1e-15f) continue;
-      for (int sg = -1; sg <= 1; sg += 2) {
-        const float x = (sg * size[ax] - lp[ax]) / lv[ax];
-        if (x < 0) continue;
-        const int a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
-        if (fabsf(lp[a1] + x * lv[a1]) <= size[a1] && fabsf(lp[a2] + x * lv[a2]) <= size[a2] && (best < 0 || x < best)) best = x;
-      }
-    }
-    return best;
-  }
-  if (type == RT_CAPSULE) {   // the cylinder's side between the caps, then the two end spheres beyond them
-    float best = -1.f;
-    const float a = lv[0] * lv[0] + lv[1] * lv[1], b = lv[0] * lp[0] + lv[1] * lp[1], c = lp[0] * lp[0] + lp[1] * lp[1] - size[0] * size[0];
-    if (a > 1e-15f) {
-      float det = b * b - a * c;
-      if (det >= 1e-15f) {
-        det = sqrtf(det);
-        for (int sgn = -1; sgn <= 1; sgn += 2) {
-          const float x = (-b + sgn * det) / a;
-          if (x >= 0 && fabsf(lp[2] + x * lv[2]) <= size[1] && (best < 0 || x < best)) best = x;
-        }
-      }
-    }
-    for (int sg = -1; sg <= 1; sg += 2) {
-      const float q[3] = {lp[0], lp[1], lp[2] - sg * size[1]};
-      const float aa = dot3(lv, lv), bb = dot3(lv, q), cc = dot3(q, q) - size[0] * size[0];
-      float dd = bb * bb - aa * cc;
-      if (dd < 1e-15f) continue;
-      dd = sqrtf(dd);
-      for (int sgn = -1; sgn <= 1; sgn += 2) {
-        const float x = (-bb + sgn * dd) / aa;
-        if (x >= 0 && sg * (lp[2] + x * lv[2]) >= size[1] && (best < 0 || x < best)) best = x;
-      }
-    }
-    return best;
-  }
-  if (type == RT_ELLIPSOID) {
-    const float sc[3] = {1.f / size[0], 1.f / size[1], 1.f / size[2]};
-    const float v[3] = {lv[0] * sc[0], lv[1] * sc[1], lv[2] * sc[2]}, q[3] = {lp[0] * sc[0], lp[1] * sc[1], lp[2] * sc[2]};
-    return ray_quad(dot3(v, v), dot3(v, q), dot3(q, q) - 1.f);
-  }
-  return -1.f;
-}
-
 // 2-D lidar.  Replaces the 360 rangefinder sensors mj_step evaluates (mujoco_server_sensor_manager.py:77-83 reads them):
 // [MJ] mj_sensorPos -> mj_ray from each site along its +Z against every geom (all groups, alpha > 0, both sides), the site's
 // own body excluded, -1 when nothing is hit, clipped to the sensor cutoff.  One workgroup per env, one thread per ray; geoms
@@ -384,7 +219,8 @@ __global__ __launch_bounds__(384) void smj_lidar_kernel(const DevRender R, const
       if (G.type != RT_PLANE) {   // bounding sphere (vec is a unit vector)
         const float oc[3] = {G.cen[0] - pnt[0], G.cen[1] - pnt[1], G.cen[2] - pnt[2]};
         const float b = dot3(oc, vec), r = G.rbound;
-        if (dot3(oc, oc) - b * b > r * r || b + r < 0.f || b - r > lim) continue;
+        const float q[3] = {oc[0] - b * vec[0], oc[1] - b * vec[1], oc[2] - b * vec[2]};   // (|oc|^2 - b^2 cancels at range: in fp32 it rejects a 1 cm sphere 9.9 m away for 1 in 10^4 of the rays that pass within 0.9 r of its centre)
+        if (dot3(q, q) > r * r || b + r < 0.f || b - r > lim) continue;
       }
       const float dif[3] = {pnt[0] - G.pos[0], pnt[1] - G.pos[1], pnt[2] - G.pos[2]};
       float lp[3], lv[3];

@@ -248,7 +248,8 @@ def ray_triangles(orig, dirs, tri, chunk=20000):
 
 
 def _ray_primitive(t, size, lp, lv):
-    """[MJ] mj_rayGeom for plane/sphere/cylinder/box in the geom frame (same rules as the kernels); -1 if no hit."""
+    """[MJ] mj_rayGeom for every primitive type (plane, sphere, capsule, ellipsoid, cylinder, box) in the geom frame, either side of a
+    surface (same rules as the kernels); -1 if no hit."""
     def quad(a, b, c):
         det = b * b - a * c
         if det < MINVAL:
@@ -283,6 +284,34 @@ def _ray_primitive(t, size, lp, lv):
                 if x >= 0 and abs(lp[a1] + x * lv[a1]) <= size[a1] and abs(lp[a2] + x * lv[a2]) <= size[a2] and (best < 0 or x < best):
                     best = x
         return best
+    if t == GEOM_CAPSULE:   # the cylinder's side between the caps, then the two end spheres beyond them
+        best = -1.0
+        a, b, c = lv[0] ** 2 + lv[1] ** 2, lv[0] * lp[0] + lv[1] * lp[1], lp[0] ** 2 + lp[1] ** 2 - size[0] ** 2
+        cand = []
+        if a > MINVAL and b * b - a * c >= MINVAL:
+            det = math.sqrt(b * b - a * c)
+            cand += [x for x in ((-b - det) / a, (-b + det) / a) if abs(lp[2] + x * lv[2]) <= size[1]]
+        for sg in (-1, 1):
+            q = np.array([lp[0], lp[1], lp[2] - sg * size[1]])
+            aa, bb, cc = lv @ lv, lv @ q, q @ q - size[0] ** 2
+            if bb * bb - aa * cc >= MINVAL:
+                det = math.sqrt(bb * bb - aa * cc)
+                cand += [x for x in ((-bb - det) / aa, (-bb + det) / aa) if sg * (lp[2] + x * lv[2]) >= size[1]]
+        for x in cand:
+            if x >= 0 and (best < 0 or x < best):
+                best = x
+        return best
+    if t == GEOM_ELLIPSOID:   # a unit sphere in the frame scaled by the semi-axes
+        v, q = lv / size, lp / size
+        return quad(v @ v, v @ q, q @ q - 1.0)
+    if t == GEOM_PLANE:   # from the front only, inside the half sizes that are positive
+        if lv[2] > -MINVAL:
+            return -1.0
+        x = -lp[2] / lv[2]
+        if x < 0:
+            return -1.0
+        px, py = lp[0] + x * lv[0], lp[1] + x * lv[1]
+        return x if (size[0] <= 0 or abs(px) <= size[0]) and (size[1] <= 0 or abs(py) <= size[1]) else -1.0
     return -1.0
 
 
@@ -1173,7 +1202,7 @@ def _lidar_static_impl(m, mesh_cache, G_mesh_names, lidar_sites):
             d = ray_triangles(lo[cand], ld[cand], tri)
             hit = d >= 0
             best[cand[hit]] = np.minimum(best[cand[hit]], d[hit])
-        elif t != GEOM_PLANE:
+        else:
             for i in range(n):
                 x = _ray_primitive(t, m["geom_size"][g], lo[i], ld[i])
                 if x >= 0:

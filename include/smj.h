@@ -157,7 +157,9 @@ int smj_base_controller_tick(smj_ctx* ctx, void* stream);
  * "primary_rows" (0 = the variant's own limit; tests lower it to force hand-overs to the larger variant),
  * "lean_build" (default 1: a Newton call of the standard variant that binds neither the debug nor the profiling slot, on a model with one
  * tree root and "manifold_cache" 0, runs a build of the step kernel with the paths such a call cannot take compiled out -- the same results
- * bit for bit; 0: every call runs the general build; smj_build.h smj_last_build says which one a call ran),
+ * bit for bit, with the collision stage on a second wavefront per env beside the tree stages; 0: every call runs the general build; 2: as 1,
+ * with the lean build that keeps the whole step on one wavefront per env -- the same states again, for A/B runs; smj_build.h smj_last_build
+ * says which one a call ran),
  * "sep_cache" (default 1: a convex pair found disjoint keeps the separating direction and tests it first on the next steps --
  * a proof of disjointness whatever the entry holds, so results do not depend on the option),
  * "depth_raster" (default 1: smj_render_depth draws meshes and boxes with the meshlet rasteriser and resolves the remaining

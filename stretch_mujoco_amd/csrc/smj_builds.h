@@ -83,13 +83,26 @@
 // first job of every step).  Same states bit for bit as `sat32` (option newton_two_waves = 0 selects that one).
 #define SMJ_ROW_sat32   SMJ_FAM_SAT32, SMJ_CARRIES_BOTH,   SMJ_CARRIES_BOTH,   1, 1, 0
 #define SMJ_ROW_sat32n  SMJ_FAM_SAT32, SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 2, 1, 0
-// The LEAN twin of `step` (smj_kernels_lean.hip): the same family, solver and wavefronts, with the paths a launch of the default model
+// The LEAN twin of `step` (smj_kernels_lean.hip): the same family and solver, with the paths a launch of the default model
 // with default options can never execute compiled out (SMJ_LEAN, smj_step_impl.h mcache_bound() .. nroot()) -- same arithmetic, same
-// results bit for bit, fewer registers held by dead code.  It is not a row the variant table routes to: smj_step swaps it in for `step`,
+// states bit for bit, fewer registers held by dead code.  It is not a row the variant table routes to: smj_step swaps it in for `step`,
 // call by call, when smj_variants.h smj_lean_eligible says every folded predicate has its folded value; hand-over target, pollers and
 // sweep stay those of the standard variant.  Hence its own list: SMJ_BUILDS stays the set of builds smj_route chooses among.
+// It runs TWO wavefronts per env (a lean row with waves = 2 turns on SMJ_W2_COLLISION, smj_step_impl.h): per step the second wavefront
+// runs the whole collision stage -- which reads only the poses kinematics() left and writes only the contact list -- beside the first
+// one's com_crb(), smooth_forces() and the contact-free head of make_constraint(); one join barrier before the contact rows.  One
+// wavefront builds the list in table order, so the states are those of the one-wavefront build and of `step` BIT FOR BIT
+// (tests/test_gpu_lean.py, tests/test_gpu_lean_two_waves.py).  Four envs per CU still (TreeTmp moves over dead rows of J, the mailbox into
+// bytes freed in the contact list: 32 LDS granules), so two waves share a SIMD and the kernel is held to 256 registers per lane
+// (amdgpu_waves_per_eu(2, 2), smj_step_tu.h).  Measured +5 % env-steps/s on the headline workload (profiles/std_two_waves_ab.txt).
 #define SMJ_LEAN_BUILDS(X) X(lean)
-#define SMJ_ROW_lean    SMJ_FAM_STD,   SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 1, 0, 0
+#define SMJ_ROW_lean    SMJ_FAM_STD,   SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 2, 0, 0
+// The lean build on ONE wavefront per env (smj_kernels_lean2.hip: the same unit under another tag, the whole step in series at the full
+// register budget) -- what `lean` was before it took the second wavefront.  Option lean_build = 2 selects it in `lean`'s place
+// (smj_variants.h smj_lean_pick): the comparator of A/B runs and of the bit-for-bit tests.  Its own list: neither SMJ_BUILDS nor
+// SMJ_LEAN_BUILDS grows.
+#define SMJ_LEAN_TWIN_BUILDS(X) X(lean2)
+#define SMJ_ROW_lean2   SMJ_FAM_STD,   SMJ_CARRIES_NEWTON, SMJ_CARRIES_NEWTON, 1, 0, 0
 #define smj_step_kernel_step smj_step_kernel   // build `step` keeps the plain symbol names
 #define smj_launch_step_step smj_launch_step
 
@@ -220,4 +233,5 @@ enum SmjBuildId {
 #define X(tag) extern const SmjBuildDesc smj_build_##tag;
 SMJ_BUILDS(X)
 SMJ_LEAN_BUILDS(X)
+SMJ_LEAN_TWIN_BUILDS(X)
 #undef X

@@ -621,7 +621,7 @@ int smj_step(smj_ctx* c, int nsteps, unsigned read_flags, void* stream) {
   const SmjVariant& V = smj_variants[c->variant];
   const SmjCallFacts facts{c->num_envs, nsteps, st.debug != nullptr, st.prof != nullptr, c->has_esc};
   const SmjRoute route = smj_route_lean(smj_route(c->variant, c->model.solver, facts.prof_bound, c->opt.newton_two_waves, c->opt.pgs_two_waves, smj_builds),
-                                        smj_lean_facts(c->model, st, c->opt.lean_build), smj_builds[SMJ_B_step], &smj_build_lean);
+                                        smj_lean_facts(c->model, st, c->opt.lean_build), smj_builds[SMJ_B_step], smj_lean_pick(c->opt.lean_build, &smj_build_lean, &smj_build_lean2));
   const SmjStepPlan plan = smj_plan_step(V, route, c->opt, facts);
   c->last_primary = route.primary;
   if (plan.esc) {   // the escalation target runs with the same options

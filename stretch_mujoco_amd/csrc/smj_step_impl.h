@@ -50,7 +50,16 @@ enum { CT_EQUALITY = 0, CT_FRICTION = 1, CT_LIMIT = 3, CT_CONTACT_FRICTIONLESS =
 #ifndef SMJ_W2_INTEGRATE
 #define SMJ_W2_INTEGRATE SMJ_SPLIT_COLLIDE
 #endif
-struct TreeTmp {  // lives in the A region until A is built
+// Two wavefronts per env in the LEAN build of the standard family (smj_builds.h: a lean row with waves = 2): the second wavefront runs
+// the WHOLE collision stage -- plane pairs, then the convex pairs, table order, alone -- beside the first one's com_crb(),
+// smooth_forces() and the contact-free head of make_constraint() (run(), collide_helper()).  One wavefront builds the contact list, so
+// nothing of SMJ_SPLIT_COLLIDE's slot claiming, list merging or serial redo is needed; that macro stays 0 here.
+#if defined(SMJ_LEAN) && defined(SMJ_TWO_WAVES) && defined(SMJ_ONLY_NEWTON) && !(NSAT > 0) && !defined(SMJ_EMUL)
+#define SMJ_W2_COLLISION 1
+#else
+#define SMJ_W2_COLLISION 0
+#endif
+struct TreeTmp {  // lives in the A region until A is built (SMJ_W2_COLLISION: over rows 0..48 of J, see SMJ_TT)
   float cinert[NBP][10], crb[NBP][10], cvel[NBP][6], cfrc[NBP][6], buf[NVP][6], cdof[NVP][6], cdof_dot[NVP][6];
 };
 
@@ -78,6 +87,9 @@ struct Smem {
   int cdim[NCON], cefc[NCON];
   unsigned short cgeom1[NCON], cgeom2[NCON];
   int cpair[NCON];      // the contact's pair (index in the model's pair list): MuJoCo's contact order, which the PGS sweeps follow
+#elif SMJ_W2_COLLISION
+  int cdim[NCON], cefc[NCON];
+  unsigned short cgeom1[NCON], cgeom2[NCON];   // (as the satellite builds have them: the 64 bytes this frees hold the mailbox below inside 32 LDS granules)
 #else
   int cdim[NCON], cgeom1[NCON], cgeom2[NCON], cefc[NCON];
 #endif
@@ -146,9 +158,24 @@ struct Smem {
   // mailbox of the env's two wavefronts (helper()): [0] command; [1] the env (first command of a launch) / the cone mask's low word;
   // [2] the second wavefront's contact count / the cone mask's high word; [3] its flags.  (The last 16 bytes of the 80 KB.)
   int mbox[4];
+#elif SMJ_W2_COLLISION
+  // mailbox of the env's two wavefronts (collide_helper()): [0] command; [1] the env; [2] the second wavefront's contact count; [3] its flags
+  int mbox[4];
 #endif
   SMJ_DEV float* A(int cap) { return &J[cap][0]; }   // PGS: A = Y D^-1 Y' + R as a packed lower triangle of cap (cap + 1) / 2 floats behind the rows a step may use (cap = NEFC_P: the union's start)
 };
+#if SMJ_W2_COLLISION
+// Tree temporaries and collision scratch are live at once here, so TreeTmp cannot share the union: it lies over rows 0..48 of J, dead
+// from the end of the Newton solve to make_constraint(), which clears rows 0..63 at its start on every step (the zero rows the MFMA
+// k-steps rely on).  The env still takes 32 LDS granules of 1280 B: four envs per CU.
+#define SMJ_TT_ROWS 49
+static_assert(sizeof(TreeTmp) <= sizeof(float) * SMJ_TT_ROWS * JS && SMJ_TT_ROWS <= 64 && SMJ_TT_ROWS <= NEFC, "TreeTmp must fit the rows of J that every make_constraint() clears");
+static_assert(offsetof(Smem, J) % 16 == 0, "make_constraint() clears J with 16-byte stores");
+static_assert(sizeof(Smem) <= 40960, "the standard family's 32 LDS granules per env");
+#define SMJ_TT (*reinterpret_cast<TreeTmp*>(&s.J[0][0]))
+#else
+#define SMJ_TT s.u.t   // the tree temporaries of com_crb() / smooth_forces(), where `s` is the env's Smem: in the stage-local union
+#endif
 // Row passes of the Newton path: rows 0..63 on lanes 0..63 (rb = 0), then rows 64..NEFC-1 on lanes 0..NEFC-65 (rb = 64), the
 // second pass only for an env that has that many rows (wave-uniform test).
 #define ROWPASS(rb, ne) _Pragma("unroll") for (int rb = 0; rb < NEFC; rb += 64) if (rb == 0 || __builtin_expect((ne) > rb, 0))
@@ -801,7 +828,7 @@ struct StepKernel {
         mulmat3(T, RI, Rt);
         float dif[3] = {xip[lane][0] - s.com[b][0], xip[lane][1] - s.com[b][1], xip[lane][2] - s.com[b][2]};
         const float mass = I[9], dd = dot3(dif, dif);
-        float* c = s.u.t.cinert[b];
+        float* c = SMJ_TT.cinert[b];
         c[0] = T[0] + mass * (dd - dif[0] * dif[0]); c[1] = T[4] + mass * (dd - dif[1] * dif[1]);
         c[2] = T[8] + mass * (dd - dif[2] * dif[2]); c[3] = T[1] - mass * dif[0] * dif[1];
         c[4] = T[2] - mass * dif[0] * dif[2]; c[5] = T[5] - mass * dif[1] * dif[2];
@@ -819,7 +846,7 @@ struct StepKernel {
           for (int x = 0; x < 3; x++) c[x] = s.xaxis[d][x];
           cross3(c + 3, s.xaxis[d], off);
         }
-        for (int x = 0; x < 6; x++) s.u.t.cdof[d][x] = c[x];
+        for (int x = 0; x < 6; x++) SMJ_TT.cdof[d][x] = c[x];
         qvel_r[lane] = s.qvel[d];
       } else {
         for (int x = 0; x < 6; x++) cdof[lane][x] = 0;
@@ -831,7 +858,7 @@ struct StepKernel {
     // (k_body_jump, as in kinematics) instead of a loop over up to 26 ancestor dofs per lane.
     LANES {
       if (lane < nv)
-        for (int x = 0; x < 6; x++) s.u.t.buf[lane][x] = cdof[lane][x] * qvel_r[lane];
+        for (int x = 0; x < 6; x++) SMJ_TT.buf[lane][x] = cdof[lane][x] * qvel_r[lane];
     }
     SYNC();
     PL<float[6]> cvb;
@@ -843,10 +870,10 @@ struct StepKernel {
         for (int u = 0; u < 6; u++) {   // a body carries at most six dofs; fixed trip count, masked tail
           const float on = u < dn ? 1.f : 0.f;
           const int a = da + (u < dn ? u : 0);
-          for (int x = 0; x < 6; x++) sv[x] += on * s.u.t.buf[dn > 0 ? a : 0][x];
+          for (int x = 0; x < 6; x++) sv[x] += on * SMJ_TT.buf[dn > 0 ? a : 0][x];
         }
       }
-      for (int x = 0; x < 6; x++) { cvb[lane][x] = sv[x]; if (lane < NBP) s.u.t.cvel[lane][x] = sv[x]; }
+      for (int x = 0; x < 6; x++) { cvb[lane][x] = sv[x]; if (lane < NBP) SMJ_TT.cvel[lane][x] = sv[x]; }
     }
     SYNC();
 #pragma unroll
@@ -857,12 +884,12 @@ struct StepKernel {
       LANES {
         const int a = bt.jump[lane][r];
         anc[lane] = a;
-        for (int x = 0; x < 6; x++) up[lane][x] = s.u.t.cvel[a][x];
+        for (int x = 0; x < 6; x++) up[lane][x] = SMJ_TT.cvel[a][x];
       }
       SYNC();
       LANES {
         if (anc[lane] > 0)
-          for (int x = 0; x < 6; x++) { cvb[lane][x] += up[lane][x]; s.u.t.cvel[lane][x] = cvb[lane][x]; }
+          for (int x = 0; x < 6; x++) { cvb[lane][x] += up[lane][x]; SMJ_TT.cvel[lane][x] = cvb[lane][x]; }
       }
       SYNC();
     }
@@ -872,18 +899,18 @@ struct StepKernel {
       if (lane < nv) {
         const int b = dt.body[lane], pb = M.body_parentid[b], da = M.body_dofadr[b];
         float cv[6];
-        for (int x = 0; x < 6; x++) cv[x] = s.u.t.cvel[pb][x];
+        for (int x = 0; x < 6; x++) cv[x] = SMJ_TT.cvel[pb][x];
         const uint64_t mk = dt.velmask[lane];
 #pragma unroll
         for (int u = 0; u < 5; u++) {
           const int a = da + u;
           const float on = (a < lane && ((mk >> a) & 1)) ? 1.f : 0.f;
-          for (int x = 0; x < 6; x++) cv[x] += on * s.u.t.buf[a < lane ? a : lane][x];
+          for (int x = 0; x < 6; x++) cv[x] += on * SMJ_TT.buf[a < lane ? a : lane][x];
         }
         const int jt = dt.jtype[lane], k = lane - dt.first[lane];
         if (jt == JT_FREE && k < 3) { for (int x = 0; x < 6; x++) cdof_dot[lane][x] = 0; }
         else cross_motion(cdof_dot[lane], cv, cdof[lane]);
-        for (int x = 0; x < 6; x++) s.u.t.cdof_dot[lane][x] = cdof_dot[lane][x];
+        for (int x = 0; x < 6; x++) SMJ_TT.cdof_dot[lane][x] = cdof_dot[lane][x];
       } else {
         for (int x = 0; x < 6; x++) cdof_dot[lane][x] = 0;
       }
@@ -900,22 +927,22 @@ struct StepKernel {
               const bool in = x0 + u < sub;
               const int x = lane + (in ? x0 + u : 0);
               const float on = in ? 1.f : 0.f;
-              for (int k = 0; k < 10; k++) cr[lane][k] += on * s.u.t.cinert[x][k];
+              for (int k = 0; k < 10; k++) cr[lane][k] += on * SMJ_TT.cinert[x][k];
             }
           }
         }
       }
       LANES {
         if (lane < nb)
-          for (int k = 0; k < 10; k++) s.u.t.crb[lane][k] = cr[lane][k];
+          for (int k = 0; k < 10; k++) SMJ_TT.crb[lane][k] = cr[lane][k];
       }
     }
     SYNC();
     LANES {
       if (lane < nv) {
         float bf[6];
-        mul_inert_vec(bf, s.u.t.crb[dt.body[lane]], cdof[lane]);
-        for (int x = 0; x < 6; x++) s.u.t.buf[lane][x] = bf[x];
+        mul_inert_vec(bf, SMJ_TT.crb[dt.body[lane]], cdof[lane]);
+        for (int x = 0; x < 6; x++) SMJ_TT.buf[lane][x] = bf[x];
       }
     }
     SYNC();
@@ -925,7 +952,7 @@ struct StepKernel {
         const int i = et.i[lane][t], j = et.j[lane][t];
         if (i < 0) continue;
         float v = 0;
-        for (int x = 0; x < 6; x++) v += s.u.t.cdof[j][x] * s.u.t.buf[i][x];
+        for (int x = 0; x < 6; x++) v += SMJ_TT.cdof[j][x] * SMJ_TT.buf[i][x];
         if (i == j) { v += et.arm[lane][t]; s.Mdiag[i] = v; }
         s.MM[i][j] = v;
         if (i != j) s.MM[j][i] = v;
@@ -1007,9 +1034,9 @@ struct StepKernel {
           for (int k = 0; k < 3; k++) { off[k] = pt[k] + s.xpos[b][k] - s.com[b][k]; F[k] = -M.gravity[k] * gm; }
           mlo = at.gc_mlo[lane]; mhi = at.gc_mhi[lane];
         }
-        float* o = s.u.t.buf[lane];     // buf[slot] = off, F ; cfrc is free until the RNE pass below
+        float* o = SMJ_TT.buf[lane];     // buf[slot] = off, F ; cfrc is free until the RNE pass below
         for (int k = 0; k < 3; k++) { o[k] = off[k]; o[3 + k] = F[k]; }
-        s.u.t.cfrc[lane][0] = __builtin_bit_cast(float, mlo); s.u.t.cfrc[lane][1] = __builtin_bit_cast(float, mhi);
+        SMJ_TT.cfrc[lane][0] = __builtin_bit_cast(float, mlo); SMJ_TT.cfrc[lane][1] = __builtin_bit_cast(float, mhi);
       }
     }
     SYNC();
@@ -1018,8 +1045,8 @@ struct StepKernel {
         float acc = 0;
 #pragma unroll
         for (int t = 0; t < 16; t++) {
-          const uint64_t mk = mk64(__builtin_bit_cast(int, s.u.t.cfrc[t][0]), __builtin_bit_cast(int, s.u.t.cfrc[t][1]));
-          const float* o = s.u.t.buf[t];
+          const uint64_t mk = mk64(__builtin_bit_cast(int, SMJ_TT.cfrc[t][0]), __builtin_bit_cast(int, SMJ_TT.cfrc[t][1]));
+          const float* o = SMJ_TT.buf[t];
           float tv[3];
           cross3(tv, cdof[lane], o);
           const float v = (cdof[lane][3] + tv[0]) * o[3] + (cdof[lane][4] + tv[1]) * o[4] + (cdof[lane][5] + tv[2]) * o[5];
@@ -1033,7 +1060,7 @@ struct StepKernel {
     // pointer jumping up the tree), body force, subtree sum projected on cdof  [MJ] mj_rne(flg_acc=0)
     LANES {
       if (lane < nv)
-        for (int x = 0; x < 6; x++) s.u.t.buf[lane][x] = s.u.t.cdof_dot[lane][x] * s.qvel[lane];
+        for (int x = 0; x < 6; x++) SMJ_TT.buf[lane][x] = SMJ_TT.cdof_dot[lane][x] * s.qvel[lane];
     }
     SYNC();
     PL<float[6]> ca;
@@ -1045,10 +1072,10 @@ struct StepKernel {
         for (int u = 0; u < 6; u++) {
           const float on = u < dn ? 1.f : 0.f;
           const int a = dn > 0 ? da + (u < dn ? u : 0) : 0;
-          for (int x = 0; x < 6; x++) sv[x] += on * s.u.t.buf[a][x];
+          for (int x = 0; x < 6; x++) sv[x] += on * SMJ_TT.buf[a][x];
         }
       }
-      for (int x = 0; x < 6; x++) { ca[lane][x] = sv[x]; if (lane < NBP) s.u.t.cfrc[lane][x] = sv[x]; }
+      for (int x = 0; x < 6; x++) { ca[lane][x] = sv[x]; if (lane < NBP) SMJ_TT.cfrc[lane][x] = sv[x]; }
     }
     SYNC();
 #pragma unroll
@@ -1059,12 +1086,12 @@ struct StepKernel {
       LANES {
         const int a = bt.jump[lane][r];
         anc[lane] = a;
-        for (int x = 0; x < 6; x++) up[lane][x] = s.u.t.cfrc[a][x];
+        for (int x = 0; x < 6; x++) up[lane][x] = SMJ_TT.cfrc[a][x];
       }
       SYNC();
       LANES {
         if (anc[lane] > 0)
-          for (int x = 0; x < 6; x++) { ca[lane][x] += up[lane][x]; s.u.t.cfrc[lane][x] = ca[lane][x]; }
+          for (int x = 0; x < 6; x++) { ca[lane][x] += up[lane][x]; SMJ_TT.cfrc[lane][x] = ca[lane][x]; }
       }
       SYNC();
     }
@@ -1075,11 +1102,11 @@ struct StepKernel {
         if (b > 0) {
           const float a[6] = {ca[lane][0], ca[lane][1], ca[lane][2], ca[lane][3] - M.gravity[0], ca[lane][4] - M.gravity[1], ca[lane][5] - M.gravity[2]};
           float t2[6];
-          mul_inert_vec(t1, s.u.t.cinert[b], a);
-          mul_inert_vec(t2, s.u.t.cinert[b], s.u.t.cvel[b]);
-          cross_force(cf, s.u.t.cvel[b], t2);
+          mul_inert_vec(t1, SMJ_TT.cinert[b], a);
+          mul_inert_vec(t2, SMJ_TT.cinert[b], SMJ_TT.cvel[b]);
+          cross_force(cf, SMJ_TT.cvel[b], t2);
         }
-        for (int x = 0; x < 6; x++) s.u.t.cfrc[b][x] = t1[x] + cf[x];
+        for (int x = 0; x < 6; x++) SMJ_TT.cfrc[b][x] = t1[x] + cf[x];
       }
     }
     SYNC();
@@ -1095,7 +1122,7 @@ struct StepKernel {
               const bool in = x0 + u < sub;
               const int x = b + (in ? x0 + u : 0);
               const float on = in ? 1.f : 0.f;
-              for (int k = 0; k < 6; k++) cfs[lane][k] += on * s.u.t.cfrc[x][k];
+              for (int k = 0; k < 6; k++) cfs[lane][k] += on * SMJ_TT.cfrc[x][k];
             }
           }
         }
@@ -2987,6 +3014,38 @@ struct StepKernel {
 #undef CTICK
   }
 
+#if SMJ_W2_COLLISION
+  // The env's second wavefront in the two-wavefront lean build.  Protocol as helper()'s (smj_kernels_sat2.hip): it waits at a workgroup
+  // barrier for a job (the command in the mailbox; the kernel enters here behind the first of those barriers, smj_step_tu.h), does it,
+  // meets the first wavefront at a second barrier where the results change hands, and leaves when the first one ends the launch.  Its one
+  // job is the collision stage exactly as run() calls it on one wavefront: collision(), then collision_convex(), pairs in table order.
+  // (run()'s second pass over the convex pairs needs kept manifolds, which SMJ_LEAN folds away: one call is the whole stage.)  It reads
+  // the poses kinematics() left (xpos, xquat, xmat) and the model's records, and writes the contact list and the collision scratch of
+  // the union (u.c, u.p) -- nothing the first wavefront touches before the join.  Of its lane-private members only ncon and flags
+  // travel, through the mailbox.
+  enum { W2_COLLIDE_ALL = 1, W2_EXIT = 2 };
+  SMJ_DEV void collide_helper() {
+    for (;;) {
+      flags = 0;
+      collision();
+      collision_convex(nullptr, false);
+      LANES { if (lane == 0) { s.mbox[2] = ncon; s.mbox[3] = flags; } }
+      WG_BARRIER();   // the first wavefront takes the contact list over (join2())
+      WG_BARRIER();   // its next step (fork2()), or the end of the launch
+      if (uni(s.mbox[0]) == W2_EXIT) return;
+    }
+  }
+  SMJ_DEV void fork2(int cmd, int w1) {
+    LANES { if (lane == 0) { s.mbox[0] = cmd; s.mbox[1] = w1; } }
+    WG_BARRIER();
+  }
+  SMJ_DEV void join2() {
+    WG_BARRIER();
+    ncon = uni(s.mbox[2]);
+    flags |= uni(s.mbox[3]);
+  }
+#endif
+
   // ------------------------------------------------------------------ B.4 constraint rows
   SMJ_DEV void make_constraint() {
     const int nv = M.nv, neq = M.neq, nfric = M.nfric, nlimit = M.nlimit;
@@ -3069,6 +3128,9 @@ struct StepKernel {
     row0 += popc64(lm);
     if (row0 > cap) { row0 = cap; flags |= SMJ_FLAG_EFC_OVERFLOW; }
     SYNC();
+#if SMJ_W2_COLLISION
+    join2();   // nothing above needs a contact; from here on the list the second wavefront built (collide_helper()) is this one's
+#endif
     // contact rows.  Phase 1, lane = contact: everything that needs model tables (body ids, dof masks, diagonal
     // approximations) is gathered at once instead of per contact in the serial loop below; rows are assigned in contact
     // order (a contact that does not fit is skipped and flagged, later smaller ones may still fit -- as before).
@@ -4758,6 +4820,77 @@ struct StepKernel {
   }
 
   // IMU: gyro + accelerometer at the IMU site from the last forward pass  [MJ] mj_sensorVel / mj_sensorAcc
+#if SMJ_BUILD_FAM == SMJ_FAM_STD
+  // The standard family: the readout must be the same bits in every build of it (tests/test_gpu_lean_two_waves.py).  Left to the
+  // compiler, the multiply-adds below were fused differently in every translation unit -- which products the vectoriser pairs decides
+  // which ones can still be contracted into the addition after them -- and `step`, `lean` and `lean2` disagreed in the last bits of gyro
+  // and accelerometer.  So here this function and the helpers it calls are compiled with contraction OFF: every product and every sum
+  // is rounded on its own, in source order, whatever surrounds the code.  (Once per launch, on the last step: the extra roundings cost
+  // nothing.)  The other families keep the function as it was, below: their code objects do not change.
+#if defined(__clang__)
+#define SMJ_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define SMJ_NO_CONTRACT
+#endif
+  SMJ_DEV static void imu_cross3(float* r, const float* a, const float* b) {
+    SMJ_NO_CONTRACT
+    const float p0 = a[1] * b[2], q0 = a[2] * b[1], p1 = a[2] * b[0], q1 = a[0] * b[2], p2 = a[0] * b[1], q2 = a[1] * b[0];
+    r[0] = p0 - q0; r[1] = p1 - q1; r[2] = p2 - q2;
+  }
+  SMJ_DEV static float imu_dot3(float a0, float a1, float a2, const float* v) {
+    SMJ_NO_CONTRACT
+    const float p0 = a0 * v[0], p1 = a1 * v[1], p2 = a2 * v[2];
+    const float s01 = p0 + p1;
+    return s01 + p2;
+  }
+  SMJ_DEV void imu() {
+    SMJ_NO_CONTRACT
+    if (M.imu_site < 0 || (!S.gyro && !staged())) return;
+    const int sid = M.imu_site, b = M.site_bodyid[sid];
+    const uint64_t mk = mk64(M.k_body_dofmask_lo[b], M.k_body_dofmask_hi[b]);
+    float cv[6], ca[6];
+    for (int x = 0; x < 6; x++) {
+      PL<float> tv, ta;
+      LANES {
+        const bool in = (mk >> lane) & 1;
+        const float pv = cdof[lane][x] * qvel_r[lane], pd = cdof_dot[lane][x] * qvel_r[lane], pa = cdof[lane][x] * qacc_r[lane];
+        tv[lane] = in ? pv : 0.f;
+        ta[lane] = in ? pd + pa : 0.f;
+      }
+      cv[x] = wave_sum(tv); ca[x] = wave_sum(ta);
+    }
+    for (int k = 0; k < 3; k++) ca[3 + k] -= M.gravity[k];
+    const float lp[3] = {M.site_pos[3 * sid], M.site_pos[3 * sid + 1], M.site_pos[3 * sid + 2]};
+    const float* X = s.xmat[b];
+    float sp[3], lm[9], R[9];
+    for (int i = 0; i < 3; i++) sp[i] = imu_dot3(X[3 * i], X[3 * i + 1], X[3 * i + 2], lp);
+    for (int k = 0; k < 9; k++) lm[k] = M.k_site_mat[9 * sid + k];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {   // R = X lm
+        const float col[3] = {lm[j], lm[3 + j], lm[6 + j]};
+        R[3 * i + j] = imu_dot3(X[3 * i], X[3 * i + 1], X[3 * i + 2], col);
+      }
+    float off[3];
+    for (int k = 0; k < 3; k++) { const float w = sp[k] + s.xpos[b][k]; off[k] = w - s.com[b][k]; }
+    float t[3], vlin[3], alin[3], c2[3], gy[3], ac[3];
+    imu_cross3(t, cv, off);
+    for (int k = 0; k < 3; k++) vlin[k] = cv[3 + k] + t[k];
+    imu_cross3(t, ca, off);
+    for (int k = 0; k < 3; k++) alin[k] = ca[3 + k] + t[k];
+    imu_cross3(c2, cv, vlin);
+    for (int k = 0; k < 3; k++) alin[k] += c2[k];
+    for (int j = 0; j < 3; j++) {   // R' cv, R' alin
+      gy[j] = imu_dot3(R[j], R[3 + j], R[6 + j], cv);
+      ac[j] = imu_dot3(R[j], R[3 + j], R[6 + j], alin);
+    }
+    if (staged()) {
+      float* st = stage_row();
+      LANES { if (lane < 3) { st[S.lay.gyro + lane] = gy[lane]; st[S.lay.accel + lane] = ac[lane]; } }
+    } else {
+      LANES { if (lane < 3) { S.gyro[lane * S.ld + env] = gy[lane]; S.accel[lane * S.ld + env] = ac[lane]; } }
+    }
+  }
+#else
   SMJ_DEV void imu() {
     if (M.imu_site < 0 || (!S.gyro && !staged())) return;
     const int sid = M.imu_site, b = M.site_bodyid[sid];
@@ -4794,6 +4927,7 @@ struct StepKernel {
       LANES { if (lane < 3) { S.gyro[lane * S.ld + env] = gy[lane]; S.accel[lane * S.ld + env] = ac[lane]; } }
     }
   }
+#endif
 
   // body poses of the last step for the ray-casting kernels (smj_render.hip: lidar, depth cameras): what mj_sensorPos /
   // mjv_updateScene read from mjData
@@ -4924,6 +5058,18 @@ struct StepKernel {
     TICK(SMJ_PROF_SETUP)
     for (int st = 0; st < nsteps; st++) {
       const bool last = st == nsteps - 1;
+#if SMJ_W2_COLLISION
+      // the collision stage on the env's second wavefront (collide_helper()) beside the tree stages and the contact-free head of
+      // make_constraint(), which joins it before its contact rows (join2()); everything else of the step is this wavefront's
+      kinematics();
+      fork2(W2_COLLIDE_ALL, env);
+      if (last && (read_flags & 4)) dump_poses();
+      com_crb();
+      if (last) dump_debug();
+      smooth_forces(last);
+      make_constraint();
+      if (last) dump_contacts();
+#else
 #if SMJ_W2_FORWARD
       fork2(W2_SAT_FORWARD, env);   // the satellites' forward pass: the second wavefront, beside the main tree's kinematics (helper())
       kinematics();
@@ -4977,6 +5123,7 @@ struct StepKernel {
 #else
       if (!newton()) nefc = NEFC;   // PGS: the A of a step with at most 64 rows sits in rows 64.. of J (solve<false>) -- have them cleared
       make_constraint();
+#endif
 #endif
       TICK(SMJ_PROF_MAKECON)
       if (S.redo && !S.redo_worker && (flags & (SMJ_FLAG_EFC_OVERFLOW | SMJ_FLAG_CON_OVERFLOW))) {

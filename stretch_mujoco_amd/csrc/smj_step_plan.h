@@ -24,7 +24,7 @@ struct SmjStepOptions {
   bool pollers_always = false; // option "pollers" < 0: send the pollers with every launch (tests)
   int newton_two_waves = 3;    // Newton on the satellite builds: bit 1 = the 16-satellite family's two-wavefront kernel (smj_kernels_sat2.hip: the second wavefront takes the moving-moving pairs and the satellites' lane-serial stages), bit 2 = the 32-satellite one's; 0 = one wavefront per env
   int pgs_two_waves = 1;       // PGS on the 16-satellite build: 1 = the two-wavefront kernel (smj_kernels_satp.hip), 0 = one wavefront per env
-  int lean_build = 1;          // 1 = a call that qualifies (smj_variants.h smj_lean_eligible) runs the lean twin of the standard Newton build, 0 = always the general build (A/B runs, tests)
+  int lean_build = 1;          // 1 = a call that qualifies (smj_variants.h smj_lean_eligible) runs the lean twin of the standard Newton build, 0 = always the general build (A/B runs, tests), 2 = as 1 with the lean build's twin on the other wavefront count (smj_builds.h SMJ_LEAN_TWIN_BUILDS)
 };
 
 // (option name of smj_set_option, field).  All are plain assignments but the two smj_set_step_option spells out.

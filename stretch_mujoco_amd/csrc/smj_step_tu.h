@@ -59,7 +59,13 @@ static __device__ __forceinline__ SmjTicket smj_take_ticket(const DevState& S, i
 }
 
 #ifndef SMJ_KERNEL_ATTR
+#if SMJ_W2_COLLISION
+// four envs per CU with two wavefronts each put two waves on every SIMD: 256 registers per lane.  __launch_bounds__(128) alone would
+// let the compiler take 512, and residency would silently fall to two envs per CU.
+#define SMJ_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
+#else
 #define SMJ_KERNEL_ATTR
+#endif
 #endif
 // The primary kernel of a variant: workgroup = one env (or one chunk of one env), no loop around run() -- a loop at this level
 // keeps the whole step pipeline's live ranges alive across its back edge and costs hundreds of bytes of scratch per lane.
@@ -81,6 +87,13 @@ __global__ __launch_bounds__(SMJ_WG_THREADS) SMJ_KERNEL_ATTR void SMJ_STEP_KERNE
     if (uni(smem.mbox[0]) == StepKernel::W2_EXIT) return;
     StepKernel h(M, S, smem, uni(smem.mbox[1]));
     h.helper();
+#elif SMJ_W2_COLLISION
+    // the env's second wavefront in the two-wavefront lean build: the collision stage of every step (smj_step_impl.h collide_helper());
+    // the first wavefront names the env with the first step's job -- or ends the launch
+    WG_BARRIER();
+    if (uni(smem.mbox[0]) == StepKernel::W2_EXIT) return;
+    StepKernel h(M, S, smem, uni(smem.mbox[1]));
+    h.collide_helper();
 #else
     // the env's second wavefront under PGS: the satellite islands' sweeps (smj_sat_pgs.h pgs_helper), nothing else
     StepKernel h(M, S, smem, 0);
@@ -103,7 +116,7 @@ __global__ __launch_bounds__(SMJ_WG_THREADS) SMJ_KERNEL_ATTR void SMJ_STEP_KERNE
   if (S.sched && threadIdx.x == 0) atomicAdd(&S.sched[SMJ_SCHED_EXITED], 1);
 #ifdef SMJ_TWO_WAVES
   // release the second wavefront (every path of the first one ends here)
-#if SMJ_SPLIT_COLLIDE
+#if SMJ_SPLIT_COLLIDE || SMJ_W2_COLLISION
   if (threadIdx.x == 0) smem.mbox[0] = StepKernel::W2_EXIT;
 #else
   if (threadIdx.x == 0) smem.sat.x[SX_MV][0][4] = __builtin_bit_cast(float, (int)StepKernel::PGS2_EXIT);

@@ -89,6 +89,9 @@ static inline SmjLeanFacts smj_lean_facts(const Model& m, const State& st, int l
 static inline bool smj_lean_eligible(const SmjLeanFacts& f) {
   return f.lean_build != 0 && f.nroot == 1 && f.manifold_cache == 0 && f.staged && !f.debug_bound && !f.prof_bound;
 }
+// Which lean build a call means: option lean_build = 2 names the twin of smj_builds.h SMJ_LEAN_TWIN_BUILDS (the other wavefront count;
+// A/B runs, tests), any other value but 0 the build tagged `lean`.  The result is smj_route_lean's `lean` argument.
+static inline const SmjBuildDesc* smj_lean_pick(int lean_build, const SmjBuildDesc* lean, const SmjBuildDesc* twin) { return lean_build == 2 && twin ? twin : lean; }
 // The route of a call with the lean twin swapped in where it may run: only for `general` (the standard variant's Newton build -- so
 // standard variant, Newton, no satellites, no profiling copy, by what smj_route chose) and only when every folded predicate holds.
 // Poller and sweep stay as routed: a step that runs out of rows is handed to the same target.

@@ -72,7 +72,20 @@ __device__ __forceinline__ float ray_leaf(const float4* T, const float* o, const
       const float q[3] = {tv[1] * e1.z - tv[2] * e1.y, tv[2] * e1.x - tv[0] * e1.z, tv[0] * e1.y - tv[1] * e1.x};
       const float v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) * id;
       if (u >= 0.f && v >= 0.f && u + v <= 1.f) {
-        const float t = (e2.x * q[0] + e2.y * q[1] + e2.z * q[2]) * id;
+        float t = (e2.x * q[0] + e2.y * q[1] + e2.z * q[2]) * id;
+        if (CULL) {
+          // Cameras: t = -(tv . n) / (d . n) with the plane's normal n from the triangle's two SHORTER edges.  e2 . (tv x e1) / det is
+          // the same number, but for a sliver whose e1 and e2 are long and nearly parallel both triple products cancel: a 2.7 m x 5 cm
+          // triangle 1.4 m away came out 6e-6 m off, 76 x the input-rounding floor ("Depth cameras against an independent
+          // reference").  The third edge w = e2 - e1 is exact to an ulp of the long ones, and e1 x e2 = e1 x w = e2 x w.
+          const float w[3] = {e2.x - e1.x, e2.y - e1.y, e2.z - e1.z};
+          const float l1 = e1.x * e1.x + e1.y * e1.y + e1.z * e1.z, l2 = e2.x * e2.x + e2.y * e2.y + e2.z * e2.z, lw = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+          const bool wl = lw >= l1 && lw >= l2, e2l = !wl && l2 >= l1;   // which edge is the longest: it stays out
+          const float a[3] = {wl || e2l ? e1.x : e2.x, wl || e2l ? e1.y : e2.y, wl || e2l ? e1.z : e2.z};
+          const float b[3] = {wl ? e2.x : w[0], wl ? e2.y : w[1], wl ? e2.z : w[2]};
+          const float n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+          t = -(tv[0] * n[0] + tv[1] * n[1] + tv[2] * n[2]) / (d[0] * n[0] + d[1] * n[1] + d[2] * n[2]);
+        }
         if (t >= tnear && t < best) best = t;
       }
     }
@@ -512,7 +525,11 @@ __global__ __launch_bounds__(256) void smj_depth_kernel(const DevRender R, const
       if (G.type != RT_PLANE) {   // bounding sphere
         const float oc[3] = {G.cen[0] - o[0], G.cen[1] - o[1], G.cen[2] - o[2]};
         const float b = dot3(oc, d), r = G.rbound;
-        if (dot3(oc, oc) * dd - b * b > r * r * dd) continue;
+        // |oc|^2 dd - b^2 subtracts two numbers of the size of the squared distance to get one of the size r^2 dd: its fp32 error is a few
+        // ulp of the first, for a 1 cm sphere 10 m away about a tenth of r^2.  The margin of 1e-6 |oc|^2 dd keeps this a superset test
+        // (the lidar kernel measures the part of oc across the ray instead, at a division per ray)
+        const float oo = dot3(oc, oc) * dd;
+        if (oo - b * b > r * r * dd + 1e-6f * oo) continue;
         if (b + r * dl < tnear * dd || b - r * dl > best * dd) continue;
       }
       STAT(1);
@@ -596,7 +613,7 @@ __global__ __launch_bounds__(256) void smj_depth_kernel(const DevRender R, const
 //  * a triangle cut by the near plane has no projection as a whole (the shell of the head around the head camera): its part beyond
 //    the plane is one or two triangles, whose screen box is what the per-pixel kernel gets together with the uncut triangle
 //    (camera frame, the env's workspace) -- it tests such triangles like primitives, per tile; so it does the handful of
-//    triangles with more than 16384 candidate pixels.  (List full: the cut triangles are rasterised here after all.)
+//    triangles with more than 16384 candidate pixels.  (List full: this kernel runs that ray test itself.)
 // Same image as the ray caster (pixel centres, front faces only, depth along the optical axis, t >= znear) up to fp32 rounding
 // and the tie-break at shared edges: tests/test_gpu_depth.py compares the two.
 __device__ __forceinline__ float rl(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
@@ -619,6 +636,29 @@ __device__ unsigned long long g_mlstat[16];
 #ifndef SMJ_ML_WAVES
 #define SMJ_ML_WAVES 4
 #endif
+// A wave shades one triangle (camera frame: v0, e1, e2) itself, lanes = the bn pixels of its box (bu0, bw0, bnu wide): the per-pixel
+// kernel's ray / triangle test; t >= znear cuts it at the near plane.  For what the hand-over list could not take.
+__device__ __forceinline__ void ml_shade_box(const float* tv0, const float* te1, const float* te2, int bu0, int bw0, int bnu, int bn, int lane,
+                                             int width, int height, float tx, float ty, float tnear, float* __restrict__ zimg) {
+  for (int i = lane; i < bn; i += 64) {
+    const int row = (int)(((float)i + 0.5f) / (float)bnu), col = i - row * bnu;
+    const float dc[3] = {(((float)(bu0 + col) + 0.5f) / width * 2.f - 1.f) * tx, (1.f - ((float)(bw0 + row) + 0.5f) / height * 2.f) * ty, -1.f};
+    const float p[3] = {dc[1] * te2[2] - dc[2] * te2[1], dc[2] * te2[0] - dc[0] * te2[2], dc[0] * te2[1] - dc[1] * te2[0]};
+    const float det = te1[0] * p[0] + te1[1] * p[1] + te1[2] * p[2];
+    if (det > 1e-30f) {
+      const float id = 1.f / det;
+      const float tv[3] = {-tv0[0], -tv0[1], -tv0[2]};
+      const float uu = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) * id;
+      const float q[3] = {tv[1] * te1[2] - tv[2] * te1[1], tv[2] * te1[0] - tv[0] * te1[2], tv[0] * te1[1] - tv[1] * te1[0]};
+      const float vv = (dc[0] * q[0] + dc[1] * q[1] + dc[2] * q[2]) * id;
+      if (uu >= 0.f && vv >= 0.f && uu + vv <= 1.f) {
+        const float tt = (te2[0] * q[0] + te2[1] * q[1] + te2[2] * q[2]) * id;
+        if (tt >= tnear) ZMIN(zimg + (long)(bw0 + row) * width + bu0 + col, tt);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMJ_ML_WAVES, 8))) void smj_meshlet_kernel(const DevRender R, float* __restrict__ ws, int width, int height,
                                                           float tan_half_fovy, float tfar_eps, float* __restrict__ zbuf, int single_image) {
   __shared__ float vx[4][SMJ_MESHLET_VERTS], vy[4][SMJ_MESHLET_VERTS], vd[4][SMJ_MESHLET_VERTS];
@@ -785,7 +825,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMJ_ML_WAVE
               // These are few but large on screen (a few centimetres from the camera): the per-pixel kernel takes the uncut triangle,
               // tile by tile inside the cut part's box (its t >= znear test does the cutting) -- measured 7 ms per render cheaper
               // than shading them here, where one wave would sit on each for hundreds of rounds.  Only if the env's list is full do
-              // the cut triangles stay in this wave (nsub).
+              // the cut triangles stay in this wave (nsub = -1).
               const float eps = 0.05f;
               const float bx0 = fminf(fminf(qx[0], qx[1]), nsub == 2 ? fminf(qx[2], qx[3]) : qx[2]), bx1 = fmaxf(fmaxf(qx[0], qx[1]), nsub == 2 ? fmaxf(qx[2], qx[3]) : qx[2]);
               const float by0 = fminf(fminf(qy[0], qy[1]), nsub == 2 ? fminf(qy[2], qy[3]) : qy[2]), by1 = fmaxf(fmaxf(qy[0], qy[1]), nsub == 2 ? fmaxf(qy[2], qy[3]) : qy[2]);
@@ -803,6 +843,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMJ_ML_WAVE
                   reinterpret_cast<int*>(E)[11] = nsub + 2;
                   for (int q = 0; q < 4; q++) { E[12 + 2 * q] = qx[q]; E[13 + 2 * q] = qy[q]; }
                   nsub = 0;
+                } else {   // the list is full: this wave shades the uncut triangle itself, below (camera frame and pixel box, in the lane)
+                  for (int q = 0; q < 3; q++) { qx[q] = cx[q]; qy[q] = cy[q]; qd[q] = pd[q]; }
+                  qx[3] = __int_as_float(hu0 | (hu1 << 16)); qy[3] = __int_as_float(hw0 | (hw1 << 16));
+                  nsub = -1;
                 }
               }
             }
@@ -818,6 +862,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMJ_ML_WAVE
       }
       MLC(3, __popcll(__ballot(k < ntri))); MLC(4, __popcll(__ballot(nsub > 0)));
       MLT(12)
+      // hand-over list full: a cut triangle (nsub < 0) gets the per-pixel kernel's ray / triangle test here, over the pixel box of its
+      // visible part; t >= znear does the cutting.  Its cut vertices lie on the near plane and project thousands of pixels off screen:
+      // rasterised from there, the fp32 edge functions and the interpolated 1 / depth lost the visible part (depths off by metres)
+      for (unsigned long long lm = __ballot(nsub < 0); lm;) {
+        const int l = __ffsll((long long)lm) - 1;
+        lm &= lm - 1;
+        float tv0[3], te1[3], te2[3];
+        tv0[0] = rl(qx[0], l); tv0[1] = rl(qy[0], l); tv0[2] = -rl(qd[0], l);
+        te1[0] = rl(qx[1], l) - tv0[0]; te1[1] = rl(qy[1], l) - tv0[1]; te1[2] = -rl(qd[1], l) - tv0[2];
+        te2[0] = rl(qx[2], l) - tv0[0]; te2[1] = rl(qy[2], l) - tv0[1]; te2[2] = -rl(qd[2], l) - tv0[2];
+        const int bu = __float_as_int(rl(qx[3], l)), bw = __float_as_int(rl(qy[3], l));
+        const int bu0 = bu & 0xffff, bw0 = bw & 0xffff, bnu = (bu >> 16) - bu0 + 1, bn = bnu * ((bw >> 16) - bw0 + 1);
+        ml_shade_box(tv0, te1, te2, bu0, bw0, bnu, bn, lane, width, height, tx, ty, tnear, zimg);
+      }
       for (int sub = 0; sub < 2; sub++) {
       if (__ballot(nsub > sub) == 0) break;            // uniform (the second pass: only waves that hold a quadrilateral)
       int u0 = 0, w0 = 0, nu = 0, npx = 0, lost = 0, npx_lost = 0;
@@ -865,23 +923,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMJ_ML_WAVE
         te2[0] = rl(px[2], l) - tv0[0]; te2[1] = rl(py[2], l) - tv0[1]; te2[2] = -rl(pd[2], l) - tv0[2];
         const int bu0 = __builtin_amdgcn_readlane(u0, l), bw0 = __builtin_amdgcn_readlane(w0, l), bnu = __builtin_amdgcn_readlane(nu, l);
         const int bn = __builtin_amdgcn_readlane(npx_lost, l);
-        for (int i = lane; i < bn; i += 64) {
-          const int row = (int)(((float)i + 0.5f) / (float)bnu), col = i - row * bnu;
-          const float dc[3] = {(((float)(bu0 + col) + 0.5f) / width * 2.f - 1.f) * tx, (1.f - ((float)(bw0 + row) + 0.5f) / height * 2.f) * ty, -1.f};
-          const float p[3] = {dc[1] * te2[2] - dc[2] * te2[1], dc[2] * te2[0] - dc[0] * te2[2], dc[0] * te2[1] - dc[1] * te2[0]};
-          const float det = te1[0] * p[0] + te1[1] * p[1] + te1[2] * p[2];
-          if (det > 1e-30f) {
-            const float id = 1.f / det;
-            const float tv[3] = {-tv0[0], -tv0[1], -tv0[2]};
-            const float uu = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) * id;
-            const float q[3] = {tv[1] * te1[2] - tv[2] * te1[1], tv[2] * te1[0] - tv[0] * te1[2], tv[0] * te1[1] - tv[1] * te1[0]};
-            const float vv = (dc[0] * q[0] + dc[1] * q[1] + dc[2] * q[2]) * id;
-            if (uu >= 0.f && vv >= 0.f && uu + vv <= 1.f) {
-              const float tt = (te2[0] * q[0] + te2[1] * q[1] + te2[2] * q[2]) * id;
-              if (tt >= tnear) ZMIN(zimg + (long)(bw0 + row) * width + bu0 + col, tt);
-            }
-          }
-        }
+        ml_shade_box(tv0, te1, te2, bu0, bw0, bnu, bn, lane, width, height, tx, ty, tnear, zimg);
       }
       const unsigned long long have = __ballot(npx > 0);
       if (have == 0) continue;       // wave-uniform

@@ -5,7 +5,8 @@
 // behind the origin.  Rays are generated in the geom's frame, in fp64, and rounded to fp32 for both sides of the comparison:
 //   (a) general poses, hits aimed at a point well inside the shape and misses aimed well outside;   (b) the origin inside;
 //   (c) exact alignments: components that are exactly 0, rays in the plane of a box face, along a cylinder's axis;
-//   (d) far and thin: r = 1, 2, 5 cm at 3, 6, 9.9 m, aimed within 0.9 r.
+//   (d) far and thin: r = 1, 2, 5 cm at 3, 6, 9.9 m, aimed within 0.9 r;
+//   (e) ray_prim with a near plane: tnear below and beyond the entry, the origin inside, unnormalised directions, planes of every bound.
 // The bound of each group is 16 x its input-rounding floor, the largest change of the fp64 answer when the ray and the sizes are
 // rounded to fp32 ("Lidar rays against an independent reference"); hit or miss must agree on every ray.  Prints "ok".
 #include "smj_ray.h"
@@ -270,6 +271,70 @@ static void check_far_and_thin() {   // (d)
   }
 }
 
+// (e) the depth cameras' form with a near plane and an unnormalised direction (pixel rays are (x, y, -1) turned into the geom's frame):
+// with tnear below the entry the entry comes back, within the bound; with tnear beyond it -1 -- never the far side; from inside -1
+static void probe_front(Group& g, int type, const double* size64, const Ray& r, int want_hit) {
+  float size[3], lp[3], lv[3];
+  double sized[3];
+  for (int k = 0; k < 3; k++) { size[k] = (float)size64[k]; sized[k] = size[k]; lp[k] = (float)r.p[k]; lv[k] = (float)r.v[k]; }
+  const Ray rr = rounded(r);
+  const double exact = ref_front(type, size64, r, 0.0), ref = ref_front(type, sized, rr, 0.0);
+  g.rays++;
+  CHECK((exact >= 0) == (want_hit != 0), "%s: type %d: the fp64 form says %g where the case was built to %s", g.name, type, exact, want_hit ? "hit" : "miss");
+  if (ref < 0) {
+    for (float tn : {0.f, 0.02f, 1.f}) CHECK(ray_prim(type, size, lp, lv, tn) < 0, "%s: type %d: a hit at tnear %g where fp64 has none", g.name, type, tn);
+    return;
+  }
+  if (exact >= 0) g.floor = std::max(g.floor, std::fabs(exact - ref));
+  for (double f : {0.0, 0.5, 0.999}) {
+    const float got = ray_prim(type, size, lp, lv, (float)(f * ref));
+    CHECK(got >= 0, "%s: type %d: entry %g lost at tnear %g", g.name, type, ref, f * ref);
+    if (got >= 0) { g.err = std::max(g.err, std::fabs((double)got - ref)); g.hits++; }
+  }
+  for (double tn : {ref * 1.001 + 1e-4, ref * 1.5, ref * 4.0})
+    CHECK(ray_prim(type, size, lp, lv, (float)tn) < 0, "%s: type %d: entry %g, tnear %g: something came back", g.name, type, ref, tn);
+}
+
+static void check_near_plane() {   // (e)
+  Group g{"(e) entering, tnear"};
+  std::mt19937 gen(15);
+  std::uniform_real_distribution<double> far(0.05, 5.0), stretch(1.0, 1.6), u(-1, 1);
+  for (int type : TYPES) {
+    double s[3];
+    sizes_of(type, s);
+    for (int i = 0; i < 2000; i++) {
+      double from[3], to[3];
+      point_at(type, s, gen, 1.0, from);
+      const double l = std::sqrt(from[0] * from[0] + from[1] * from[1] + from[2] * from[2]), d = far(gen), k = stretch(gen);
+      for (double& x : from) x *= (l + d) / l;
+      point_at(type, s, gen, 0.9, to);
+      Ray r = towards(from, to);
+      for (double& x : r.v) x *= k;
+      probe_front(g, type, s, r, 1);
+      // from inside: nothing, whatever tnear
+      point_at(type, s, gen, 0.8 * (i % 10) / 9.0, from);
+      point_at(type, s, gen, 3.0, to);
+      Ray q = towards(from, to);
+      for (double& x : q.v) x *= k;
+      probe_front(g, type, s, q, 0);
+    }
+  }
+  for (int i = 0; i < 2000; i++) {
+    const double inf[3] = {0, 0, 1}, fin[3] = {1.5, 1.0, 1}, half[3] = {0, 1.0, 1};
+    const double from[3] = {3 * u(gen), 3 * u(gen), 0.2 + 2 * std::fabs(u(gen))}, in[3] = {1.3 * u(gen), 0.9 * u(gen), 0}, out[3] = {3 * u(gen), 1.2 + std::fabs(u(gen)), 0};
+    Ray a = towards(from, in), b = towards(from, out);
+    const double k = stretch(gen);
+    for (double& x : a.v) x *= k;
+    for (double& x : b.v) x *= k;
+    probe_front(g, RT_PLANE, inf, a, 1);
+    probe_front(g, RT_PLANE, fin, a, 1);
+    probe_front(g, RT_PLANE, half, a, 1);
+    probe_front(g, RT_PLANE, half, b, 0);
+    probe_front(g, RT_PLANE, fin, b, 0);
+  }
+  finish(g);
+}
+
 static void check_quad_rule() {
   // the nearest root that is not behind the origin, -1 when the line misses or the sphere lies behind
   const float v[3] = {1, 0, 0}, ahead[3] = {-3, 0, 0}, in[3] = {0.25f, 0, 0}, behind[3] = {3, 0, 0}, beside[3] = {-3, 0.75f, 0};
@@ -286,6 +351,7 @@ int main() {
   check_origin_inside();
   check_exact_alignments();
   check_far_and_thin();
+  check_near_plane();
   if (failures) { printf("%d failures\n", failures); return 1; }
   printf("ok\n");
   return 0;

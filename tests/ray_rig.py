@@ -115,7 +115,8 @@ def _f(v):
 
 def _geom_xml(g):
     size = f'size="{_f(g["size"][:2])} 1"' if g["type"] == "plane" else (f'mesh="{g["mesh"]}"' if g["type"] == "mesh" else f'size="{_f(g["size"])}"')
-    return (f'<geom type="{g["type"]}" {size} pos="{_f(g["pos"])}" quat="{_f(g["quat"])}" rgba="0.5 0.5 0.5 {g["alpha"]}" group="{g["group"]}" '
+    name = f'name="{g["name"]}" ' if g.get("name") else ""
+    return (f'<geom {name}type="{g["type"]}" {size} pos="{_f(g["pos"])}" quat="{_f(g["quat"])}" rgba="0.5 0.5 0.5 {g["alpha"]}" group="{g["group"]}" '
             'contype="0" conaffinity="0" density="0"/>')
 
 
@@ -126,11 +127,13 @@ def mjcf(scene):
         inner += "".join(_geom_xml(g) for g in b["geoms"])
         if i == scene["laser"]:
             inner += "".join(f'<site name="ray{r:03d}" pos="{_f(p)}" quat="{_f(q)}"/>' for r, (p, q) in enumerate(scene["sites"]))
+        inner += "".join(f'<camera name="cam{k}" pos="{_f(c["pos"])}" quat="{_f(c["quat"])}" fovy="{float(c["fovy"])!r}"/>'
+                         for k, c in enumerate(scene.get("cameras", ())) if c["body"] == i)
         inner += "".join(body_xml(j) for j, c in enumerate(scene["bodies"]) if c["parent"] == i)
         return f'<body name="{b["name"]}" pos="{_f(b["pos"])}" quat="{_f(b["quat"])}">{inner}</body>'
 
     meshes = "".join(f'<mesh name="{k}" vertex="{_f(np.ravel(m["vertex"]))}" face="{" ".join(str(int(i)) for i in np.ravel(m["face"]))}"/>' for k, m in scene["meshes"].items())
-    return ('<mujoco><compiler angle="radian"/><option gravity="0 0 0"/><asset>' + meshes + '</asset><worldbody>' + "".join(_geom_xml(g) for g in scene["world"]) +
+    return ('<mujoco><compiler angle="radian"/><option gravity="0 0 0"/>' + scene.get("header", "") + '<asset>' + meshes + '</asset><worldbody>' + "".join(_geom_xml(g) for g in scene["world"]) +
             "".join(body_xml(i) for i, b in enumerate(scene["bodies"]) if b["parent"] < 0) +
             f'</worldbody><sensor><rangefinder site="ray" cutoff="{scene["cutoff"]}"/></sensor></mujoco>')
 
